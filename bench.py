@@ -8,9 +8,13 @@ all-reduce of the flat gradient buffer when N > 1, fused clip + Adam/amsgrad)
 over one batch of synthetic N(0,1) 80-mel x 128-frame segments already resident
 in HBM.  Workload = BASELINE.json configs[1]: batch 256 per GPU, fp32 (weak
 scaling: per-GPU batch fixed, global batch = 256*N).  Rank 0 prints ONE JSON
-line.  After the timed region (never inside it) two extra legs run on rank 0 at
-N = 1: a per-kernel-class HIP-event profile (-> "roofline") and the CPU oracle
-timed on the host cores (-> "cpu_baseline").
+line.  A plain run sets up, warms up, times the K steps and prints that line;
+``--dump-outputs DIR`` also writes what the last timed step computed as
+DIR/<name>.npy.  ``--full`` adds what the headline figure does not need, after
+the timed region (never inside it), on rank 0 at N = 1: a per-kernel-class
+HIP-event profile (-> "roofline"), the sub-records of the other BASELINE
+configs (child processes), a last step at fixed noise (-> "final_losses") and
+the CPU oracle timed on the host cores (-> "cpu_baseline").
 
 N > 1: one process per GPU over RCCL.  Either the caller launches the ranks
 (``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``: RANK /
@@ -45,6 +49,32 @@ FWD_GFLOP_PER_SEG = {(80, 128): 0.6519, (80, 1024): 5.206}      # SURVEY 8d (one
 def stock_config(n_mels):
     from adaptive_voice_conversion_amd.config import default_config
     return default_config(n_mels)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one out_dir/<name>.npy per array (float64 stays float64, everything else float32), 64 MB at most in all.  Over
+    the budget, every array larger than an equal share of what the smaller ones leave is replaced by a fixed, seeded sample of its
+    flattened elements (an evenly strided index set at a seeded offset: the same elements in every run of the same arguments)."""
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[k] = np.atleast_1d(v if v.dtype == np.float64 else v.astype(np.float32))
+    budget, left = DUMP_BUDGET_BYTES, dict(host)
+    for k in sorted(host, key=lambda k: host[k].nbytes):   # smallest first: kept whole while they fit their share
+        share = budget // len(left)
+        v = left.pop(k)
+        if v.nbytes > share:
+            n, m = v.size, max(1, share // v.itemsize)
+            stride = n // m
+            off = int(np.random.default_rng(0).integers(0, n - (m - 1) * stride))
+            host[k] = v.reshape(-1)[off + stride * np.arange(m)]
+        budget -= host[k].nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def profile_classes(solver, x, eps, steps):
@@ -570,13 +600,15 @@ def ragged_bench(a, dev):
     pairs = [(torch.randn(int(t), a.mels, generator=g).to(dev), torch.randn(int(c), a.mels, generator=g).to(dev)) for t, c in zip(T, Tc)]
     xs, cs = [p_[0] for p_ in pairs], [p_[1] for p_ in pairs]
 
+    last = [None]
+
     def timed(fn, steps, warmup):
         for _ in range(warmup):
             fn()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            fn()
+            last[0] = fn()
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / steps
     # cold path: real traffic almost never repeats a tuple of lengths -- every call below sees a NEW tuple (the same utterances in another
@@ -589,22 +621,26 @@ def ragged_bench(a, dev):
         inf.model.inference_ragged(xs[k:] + xs[:k], cs[k:] + cs[:k])
     with torch.no_grad():
         t_rag = timed(lambda: inf.model.inference_ragged(xs, cs), a.steps, a.warmup)
-        t_cold = timed(cold, max(3, min(a.steps, n - 2)), 1)
-        inf.model.set_plan_cache_size(inference=2 * n)
-        t_bkt = timed(lambda: inf._convert_batch_bucketed(pairs, 4), max(2, a.steps // 4), 1)
-        t_one = timed(lambda: [inf.model.inference(x.t()[None], c.t()[None]) for x, c in pairs], max(2, a.steps // 4), 1)
+        if a.dump_outputs:   # the converted [M, T''_b] mels of the last timed call, concatenated along time
+            dump_outputs(a.dump_outputs, {"converted": torch.cat(last[0], dim=1)})
+        if a.full:
+            t_cold = timed(cold, max(3, min(a.steps, n - 2)), 1)
+            inf.model.set_plan_cache_size(inference=2 * n)
+            t_bkt = timed(lambda: inf._convert_batch_bucketed(pairs, 4), max(2, a.steps // 4), 1)
+            t_one = timed(lambda: [inf.model.inference(x.t()[None], c.t()[None]) for x, c in pairs], max(2, a.steps // 4), 1)
     frames = int(T.sum())
     gflop = 0.6519 / 128 * (T.sum() * (0.2600 + 0.1324) / 0.6519 + Tc.sum() * 0.2594 / 0.6519)   # per-frame forward work of the three networks
+    config = {"workload": "SURVEY 8f-1 (BASELINE configs[3] generalised to real utterance lengths): AE.inference over "
+                          f"{n} (source, target) pairs, {frames} source frames in total", "pairs": n, "source_frames": frames,
+              "ragged_ms": 1e3 * t_rag, "compute": inf.model.last_ragged_compute, "algorithmic_tflops_ragged": gflop / t_rag / 1e3}
+    if a.full:
+        config.update({"ragged_cold_ms (a NEW tuple of lengths every call: plan creation + tables included)": 1e3 * t_cold,
+                       "bucketed_4_streams_ms (round 2: a B=1 plan per distinct shape; includes the result download)": 1e3 * t_bkt,
+                       "one_call_per_utterance_ms (the reference's loop)": 1e3 * t_one})
     print(json.dumps({"metric": f"utterances/sec, one-shot conversion of {n} pairs of different lengths (100-600 frames) in one ragged launch set",
                       "value": n / t_rag, "unit": "utterances/sec", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * t_rag,
                       "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-                      "config": {"workload": "SURVEY 8f-1 (BASELINE configs[3] generalised to real utterance lengths): AE.inference over "
-                                             f"{n} (source, target) pairs, {frames} source frames in total", "pairs": n, "source_frames": frames,
-                                 "ragged_ms": 1e3 * t_rag, "ragged_cold_ms (a NEW tuple of lengths every call: plan creation + tables included)": 1e3 * t_cold,
-                                 "compute": inf.model.last_ragged_compute,
-                                 "bucketed_4_streams_ms (round 2: a B=1 plan per distinct shape; includes the result download)": 1e3 * t_bkt,
-                                 "one_call_per_utterance_ms (the reference's loop)": 1e3 * t_one,
-                                 "algorithmic_tflops_ragged": gflop / t_rag / 1e3}}), flush=True)
+                      "config": config}), flush=True)
 
 
 def dsp_bench(a, dev):
@@ -623,33 +659,39 @@ def dsp_bench(a, dev):
     mel, _ = dsp.get_spectrograms_device(yd, do_trim=False)
     T = mel.shape[0]
 
+    last = [None]
+
     def timed(fn, steps, warmup):
         for _ in range(warmup):
             fn()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            fn()
+            last[0] = fn()
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / steps
-    t_front = timed(lambda: dsp.get_spectrograms_device(yd, do_trim=False), a.steps, a.warmup)
     t_back = timed(lambda: dsp.melspectrogram2wav(mel, do_trim=False), a.steps, a.warmup)
-    nb = a.batch if a.batch != 256 else 8      # (--batch defaults to the train step's 256)
-    mels = [mel] * nb
-    t_batch = timed(lambda: dsp.melspectrogram2wav_batch(mels, do_trim=False), max(1, a.steps // 2), 1)
+    if a.dump_outputs:   # the waveform of the last timed call
+        dump_outputs(a.dump_outputs, {"waveform": last[0]})
     F2, K = hp.n_fft + 2, hp.win_length
     flops = (2 * hp.n_iter + 1) * 2.0 * F2 * K * T + 2.0 * (hp.n_fft // 2 + 1) * hp.n_mels * T
     out = {"metric": f"utterances/sec mel -> waveform (melspectrogram2wav, {hp.n_iter} Griffin-Lim iterations, {a.seconds:g} s of {hp.sr} Hz audio = {T} frames)",
            "value": 1.0 / t_back, "unit": "utterances/sec", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * t_back,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": "SURVEY §8f row 4 (not a BASELINE.json config): mel <-> waveform DSP of one utterance, stock hyper-parameters",
-                      "frames": T, "front_end_ms (get_spectrograms, no trim)": 1e3 * t_front,
-                      f"batched: {nb} equally long utterances per call (melspectrogram2wav_batch)": {
-                          "ms_per_call": 1e3 * t_batch, "utterances_per_sec": nb / t_batch, "gemm_tflops": nb * flops / t_batch / 1e12}},
+                      "frames": T},
            "roofline": {"kernel": "conv_gemm 1x1 (the STFT / iSTFT GEMMs against the windowed DFT bases)", "bound": "mfma",
                         "achieved": flops / t_back / 1e12, "peak": 157.3, "unit": "TFLOP/s", "frac": flops / t_back / 1e12 / 157.3,
                         "traffic": None,
                         "note": "algorithmic GEMM flops of the whole call over its wall time (row kernels and launch gaps included)"}}
+    if a.full:
+        t_front = timed(lambda: dsp.get_spectrograms_device(yd, do_trim=False), a.steps, a.warmup)
+        nb = a.batch if a.batch != 256 else 8      # (--batch defaults to the train step's 256)
+        mels = [mel] * nb
+        t_batch = timed(lambda: dsp.melspectrogram2wav_batch(mels, do_trim=False), max(1, a.steps // 2), 1)
+        out["config"].update({"front_end_ms (get_spectrograms, no trim)": 1e3 * t_front,
+                              f"batched: {nb} equally long utterances per call (melspectrogram2wav_batch)": {
+                                  "ms_per_call": 1e3 * t_batch, "utterances_per_sec": nb / t_batch, "gemm_tflops": nb * flops / t_batch / 1e12}})
     if not a.no_cpu_baseline:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         from oracle import dsp_oracle as D   # the CPU restatement (numpy float64, pocketfft), timed on this host
@@ -718,7 +760,7 @@ def config2_in_child(a):
     """config2_bf16_record in a fresh process of the same interpreter (same seeds, same harness); the record says so."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--config2-worker", "--steps", str(a.steps), "--warmup", str(a.warmup), "--batch", str(a.batch),
-           "--mels", str(a.mels), "--frames", str(a.frames), "--no-cpu-baseline", "--no-config2"] + (["--no-profile"] if a.no_profile else [])
+           "--mels", str(a.mels), "--frames", str(a.frames), "--full", "--no-cpu-baseline", "--no-config2"] + (["--no-profile"] if a.no_profile else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or not lines:
@@ -737,7 +779,7 @@ def extra_config_in_child(a, name):
     argv = {"config3_infer_b1024": ["--mode", "infer", "--batch", "1024", "--frames", "128"],
             "config4_t1024_b64": ["--batch", "64", "--frames", "1024"]}[name]
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(a.steps), "--warmup", str(a.warmup), "--mels", str(a.mels),
-           "--no-cpu-baseline", "--no-config2"] + argv + (["--no-profile"] if a.no_profile else [])
+           "--full", "--no-cpu-baseline", "--no-config2"] + argv + (["--no-profile"] if a.no_profile else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or not lines:
@@ -829,16 +871,22 @@ def main():
     ap.add_argument("--dtype", choices=("f32", "bf16", "bf16s", "bf16r", "f32x3"), default="f32",
                     help="f32 = the headline (BASELINE configs[1]); bf16 = configs[2]'s compute mode (bf16 matrix products, "
                          "fp32 master weights / optimizer state) -- a separate, non-headline measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-config2", action="store_true", help="skip the config2_bf16 / config3_infer_b1024 / config4_t1024_b64 sub-records of the default (configs[1]) line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: per-kernel-class profile and rooflines, "
+                         "the config2_bf16 / config3_infer_b1024 / config4_t1024_b64 sub-records, a last step at fixed noise (final_losses), "
+                         "the CPU baseline; --mode ragged / dsp: their side measurements.  A plain run does none of these")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, 64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the per-kernel-class profile and rooflines")
+    ap.add_argument("--no-config2", action="store_true", help="with --full: skip the config2_bf16 / config3_infer_b1024 / config4_t1024_b64 sub-records of the configs[1] line")
     ap.add_argument("--single-stream", action="store_true", help="profiling aid: every kernel on the caller's stream")
     ap.add_argument("--feed", action="store_true", help="draw every batch from an HBM-resident synthetic corpus through the "
                                                         "device-side gather kernel (DeviceSegmentFeed) inside the timed loop")
     ap.add_argument("--presleep-ms", type=float, default=0.0,
                     help="tracing aid: park the GPU this long before every timed step so that the (tracer-slowed) host has "
                          "the whole step enqueued when it starts; the reported time is then meaningless")
-    ap.add_argument("--profile-json", default=None, help="write the per-kernel-class table here")
+    ap.add_argument("--profile-json", default=None, help="with --full: write the per-kernel-class table here")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for --gpus N > 1: nccl (= RCCL over xGMI, the real thing) or gloo (CUDA tensors staged through the "
                          "host: lets N ranks SHARE one GPU, which executes the multi-rank code path on a 1-GPU box; not a scaling number)")
@@ -848,6 +896,10 @@ def main():
     ap.add_argument("--config2-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-point", default="128,16,7", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if not a.full:   # a plain run: set-up, warm-up, the timed steps, the outputs if asked for, the result line
+        if a.profile_json:
+            ap.error("--profile-json needs --full")
+        a.no_cpu_baseline = a.no_profile = a.no_config2 = True
     if a.cpu_baseline_worker:
         return cpu_baseline_worker(a.mels, a.frames, tuple(int(v) for v in a.cpu_point.split(",")))
 
@@ -948,6 +1000,8 @@ def main():
             plan_i.forward(model.flat_parameters(), x, xc, None, ws_i)
         barrier()
         el, per_rank = rank_times(time.perf_counter() - t0)
+        if rank == 0 and a.dump_outputs:   # the converted mels of the last timed pass (AE.inference's result)
+            dump_outputs(a.dump_outputs, {"dec": plan_i.view(ws_i, "dec", (B, a.mels, plan_i.out_len))})
         if rank == 0:
             rec = {"metric": metric, "value": world * B * a.steps / el,
                    "unit": "utterances/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -975,7 +1029,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    plan, _ = solver.model._plan(B, T, T, dev)
+    plan, ws = solver.model._plan(B, T, T, dev)
     eps = torch.randn(B, cfg["ContentEncoder"]["c_out"], plan.latent_len, generator=g).to(dev)
     feed = None
     if a.feed:   # HBM-resident synthetic corpus (2048 utterances' worth of frames), per-rank disjoint shards
@@ -989,7 +1043,7 @@ def main():
 
     def one_step():   # the reparameterisation noise (model.py:383 `normal_`) is drawn INSIDE the step, as the reference does
         xb = next(feed) if feed is not None else x
-        solver.ae_step(xb, 1.0, sync=False)
+        return solver.ae_step(xb, 1.0, sync=False)
 
     for _ in range(a.warmup):
         one_step()
@@ -1001,13 +1055,19 @@ def main():
     for _ in range(a.steps):
         if a.presleep_ms > 0:
             torch.cuda._sleep(int(a.presleep_ms * 2.0e6))
-        one_step()
+        last = one_step()
     barrier()
     elapsed, per_rank = rank_times(time.perf_counter() - t0)
     exposed_ar = solver.exposed_allreduce_ms() if world > 1 else None
     solver.measure_allreduce = False
-    meta = solver.ae_step(x, 1.0, eps=eps, sync=True)
-    if not all(v == v and abs(v) < 1e6 for v in meta.values()):
+    # what the last timed step returned (its losses and gradient norm) and left behind (the reconstruction, the updated parameters)
+    last = {k: float(v.item()) for k, v in last.items()}
+    if not all(v == v and abs(v) < 1e6 for v in last.values()):
+        raise SystemExit(f"non-finite training state: {last}")
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, dict(last, dec=plan.view(ws, "dec", (B, a.mels, plan.out_len)), parameters=solver.model.flat_parameters()))
+    meta = solver.ae_step(x, 1.0, eps=eps, sync=True) if a.full else None   # a last step at fixed noise (--full: final_losses)
+    if meta is not None and not all(v == v and abs(v) < 1e6 for v in meta.values()):
         raise SystemExit(f"non-finite training state: {meta}")
 
     if rank == 0:
@@ -1021,10 +1081,10 @@ def main():
                        "baseline_config_index": cfg_idx, "global_batch": world * B, "segment": [a.mels, T], "parallelism": f"dp{world}",
                        "world_size": world, "dist_backend": (a.dist_backend if world > 1 else None), "per_rank_ms_per_step": [1e3 * t / a.steps for t in per_rank],
                        "exposed_allreduce_ms": exposed_ar, "allreduce_buckets": (int(cfg.get("allreduce_buckets", 3)) if world > 1 else None),
-                       "tuning": a.tune or None,
+                       "tuning": a.tune or None, "last_step": last,
                        "allreduce": ("decoder range on a communication stream under the encoders' backward, encoders' range after it; "
                                      + ("RCCL via torch.distributed nccl" if a.dist_backend == "nccl" else f"torch.distributed {a.dist_backend} (staged through the host: executes the path, not a scaling number)")) if world > 1 else None,
-                       "final_losses": meta},
+                       **({"final_losses": meta} if meta is not None else {})},
         }
         if world == 1 and not a.no_profile:
             prof = profile_classes(solver, x, eps, steps=3)
