@@ -85,9 +85,17 @@ int avc_adam_blocks(long n);
 int avc_launch_sumsq(const float* g, long n, float* partial, hipStream_t s);
 int avc_launch_clip_adam(const AdamArgs& a, hipStream_t s);
 struct avc_plan;
+// inputs of a decoder part plan (AVC_PLAN_DECODER_ONLY): the caller's z [B, c_in, Tb] and emb [B, c_cond], element strides
+struct DecIn {
+    const float* z;
+    long szb, szc;
+    int szt;
+    const float* emb;
+    long seb, sec;
+};
 int avc_backward_impl(const avc_plan*, const float*, const float*, long, long, int, const float*, long, long, int,
                       const float*, const float*, const float*, const float*, float, float*, float*, hipStream_t, bool,
-                      long*);
+                      long*, const DecIn* din = nullptr);
 
 // ---- optional per-class event timing (prof.hip)
 enum { AVC_K_CONV_FWD = 0, AVC_K_CONV_DGRAD, AVC_K_CONV_WGRAD, AVC_K_REDUCE, AVC_K_IN_FWD, AVC_K_IN_BWD, AVC_K_PACK,
@@ -108,4 +116,5 @@ int avc_launch_dense(const DenseArgs& a, int backward, hipStream_t s);
 int avc_launch_gather_segments(const float* corpus, long n_rows, int M, const long* starts, int B, int T, float* out,
                                hipStream_t s);
 int avc_launch_add_transposed(float* dst, const float* src, int B, int C, hipStream_t s);
+int avc_launch_transpose(float* dst, const float* src, int R, int C, hipStream_t s);   // dst[c][r] = src[r][c]
 

@@ -147,6 +147,7 @@ struct avc_plan {
     double pack_tab_bytes = 0;
     bool bh = false;
     long ddecp = -1, dmulsp = -1;   // pair copies of d(dec) and d(muls): the conv launches that consume them read pair operands
+    long demb_rm = -1;              // decoder part plans: d(emb) row-major [B, c_cond] (ws["d_emb"]; demb stays the GEMM's channel-major output)
 
     long alloc(long n) {
         long o = ws_top;
@@ -155,6 +156,12 @@ struct avc_plan {
     }
     const float* par(const float* params_, int idx) const { return params_ + params[idx].off; }
 };
+
+#define AVC_PLAN_PARTS (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_CONTENT_ONLY | AVC_PLAN_DECODER_ONLY)
+// which of the three networks a plan runs (part plans: one of them)
+static bool has_spk(int flags) { return !(flags & (AVC_PLAN_CONTENT_ONLY | AVC_PLAN_DECODER_ONLY)); }
+static bool has_enc(int flags) { return !(flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_DECODER_ONLY)); }
+static bool has_dec(int flags) { return !(flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_CONTENT_ONLY)); }
 
 // --------------------------------------------------------------------------
 // plan construction
@@ -273,12 +280,18 @@ extern "C" int avc_plan_create_ex(const avc_model_cfg* cfg, int B, int T, int T_
 
 extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int T_cond, int flags, const avc_tuning* tuning, avc_plan** out) {
     if (!cfg || !out || B < 1 || T < 1) return fail(-1, "avc_plan_create: bad arguments");
-    if (flags & ~(AVC_PLAN_INFERENCE | AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_X3 | AVC_PLAN_BF16S)) return fail(-1, "avc_plan_create: unknown flag");
+    if (flags & ~(AVC_PLAN_INFERENCE | AVC_PLAN_PARTS | AVC_PLAN_PART_GRADS | AVC_PLAN_X3 | AVC_PLAN_BF16S)) return fail(-1, "avc_plan_create: unknown flag");
     if ((flags & AVC_PLAN_X3) && (flags & AVC_PLAN_BF16S)) return fail(-1, "avc_plan_create: AVC_PLAN_X3 and AVC_PLAN_BF16S exclude each other");
     if (tuning && tuning->struct_size != (int)sizeof(avc_tuning)) return fail(-1, "avc_plan_create_tuned: avc_tuning of another library version (use avc_tuning_init)");
-    if (flags & AVC_PLAN_SPEAKER_ONLY) flags |= AVC_PLAN_INFERENCE;
+    const int part = flags & AVC_PLAN_PARTS;
+    if (part & (part - 1)) return fail(-1, "avc_plan_create: at most one of AVC_PLAN_SPEAKER_ONLY / _CONTENT_ONLY / _DECODER_ONLY");
+    if ((flags & AVC_PLAN_PART_GRADS) && !part) return fail(-1, "avc_plan_create: AVC_PLAN_PART_GRADS needs a part flag (whole plans have gradient buffers unless AVC_PLAN_INFERENCE)");
+    if ((flags & AVC_PLAN_PART_GRADS) && (flags & AVC_PLAN_INFERENCE)) return fail(-1, "avc_plan_create: AVC_PLAN_PART_GRADS and AVC_PLAN_INFERENCE exclude each other");
+    if (part && !(flags & AVC_PLAN_PART_GRADS)) flags |= AVC_PLAN_INFERENCE;   // a part plan is forward-only unless asked for its gradients
     if (T_cond <= 0) T_cond = T;
-    const bool infer = (flags & AVC_PLAN_INFERENCE) != 0, spk_only = (flags & AVC_PLAN_SPEAKER_ONLY) != 0;
+    const bool infer = (flags & AVC_PLAN_INFERENCE) != 0;
+    const bool dec_only = (flags & AVC_PLAN_DECODER_ONLY) != 0;
+    const bool do_spk = has_spk(flags), do_enc = has_enc(flags), do_dec = has_dec(flags);
     if (validate_enc(cfg->spk, true) || validate_enc(cfg->enc, false)) return fail(-2, "avc_plan_create: unsupported encoder config");
     const avc_decoder_cfg& dc = cfg->dec;
     if (dc.n_conv_blocks < 1 || dc.n_conv_blocks > AVC_MAX_BLOCKS || 2 * dc.n_conv_blocks > 12 || dc.kernel_size < 1 || dc.kernel_size > 8)
@@ -355,11 +368,12 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
         }
         return 0;
     };
-    if (sched_enc(p->spk, T_cond) || sched_enc(p->enc, T)) {
+    // (decoder part plans: T is the latent length Tb the caller hands in; the encoders' schedules do not exist)
+    if (!dec_only && (sched_enc(p->spk, T_cond) || sched_enc(p->enc, T))) {
         delete p;
         return fail(-6, "Padding size should be less than the corresponding input dimension");
     }
-    p->Tb = p->enc.T[p->enc.n];
+    p->Tb = dec_only ? T : p->enc.T[p->enc.n];
     d.T[0] = p->Tb;
     for (int l = 0; l < d.n; ++l) {
         if (dc.kernel_size / 2 >= d.T[l]) {
@@ -372,20 +386,22 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
     if (p->bh) {
         // pair rows: two channels per dword, four frames per 16-byte access of the row kernels
         bool ok = !((cfg->enc.c_in | cfg->enc.c_h | cfg->enc.c_bank | cfg->enc.c_out | cfg->spk.c_h | cfg->spk.c_bank | dc.c_h | dc.c_in | dc.c_out) & 1);
-        for (int l = 0; l <= p->spk.n; ++l) ok = ok && (p->spk.T[l] % 4 == 0);
-        for (int l = 0; l <= p->enc.n; ++l) ok = ok && (p->enc.T[l] % 4 == 0);
+        if (!dec_only) {
+            for (int l = 0; l <= p->spk.n; ++l) ok = ok && (p->spk.T[l] % 4 == 0);
+            for (int l = 0; l <= p->enc.n; ++l) ok = ok && (p->enc.T[l] % 4 == 0);
+            for (int l = 0; l < p->enc.n; ++l) ok = ok && (p->enc.T[l] <= 2048) && (p->spk.T[l] <= 2048);
+        }
         for (int l = 0; l <= d.n; ++l) ok = ok && (d.T[l] % 4 == 0) && (d.T[l] <= 2048);
-        for (int l = 0; l < p->enc.n; ++l) ok = ok && (p->enc.T[l] <= 2048) && (p->spk.T[l] <= 2048);
         if (!ok) {
             delete p;
             return fail(AVC_ERR_PAIR_SHAPE, "avc_plan_create: AVC_PLAN_BF16S needs even channel counts and frame counts that are multiples of 4 (<= 2048) at every level");
         }
     }
 
-    // ---- packed weights (inference plans keep no dgrad images; speaker-only plans only the speaker encoder's)
+    // ---- packed weights (inference plans keep no dgrad images; part plans only their own network's)
     const bool dg = !infer;
     for (EncNet* e : {&p->spk, &p->enc}) {
-        if (spk_only && e == &p->enc) continue;
+        if (!(e == &p->enc ? do_enc : do_spk)) continue;
         for (int id : e->bank) finish_layer(p, p->layers[id], false, 0, B, e->T[0], e->T[0], e->nb);
         finish_layer(p, p->layers[e->in_conv], dg, e->CC - e->c.c_in, B, e->T[0], e->T[0]);
         for (int l = 0; l < e->n; ++l) {
@@ -393,13 +409,13 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
             finish_layer(p, p->layers[e->c2[l]], dg, 0, B, e->T[l + 1], e->T[l]);
         }
     }
-    for (int l = 0; l < p->spk.nd; ++l) {
+    for (int l = 0; l < p->spk.nd && do_spk; ++l) {
         finish_layer(p, p->layers[p->spk.dn1[l]], dg, 0, 1, B, B, 1, false);
         finish_layer(p, p->layers[p->spk.dn2[l]], dg, 0, 1, B, B, 1, false);
     }
-    finish_layer(p, p->layers[p->spk.outl], dg, 0, 1, B, B, 1, false);
-    if (!spk_only) {
-        finish_layer(p, p->layers[p->enc.heads], dg, 0, B, p->Tb, p->Tb);
+    if (do_spk) finish_layer(p, p->layers[p->spk.outl], dg, 0, 1, B, B, 1, false);
+    if (do_enc) finish_layer(p, p->layers[p->enc.heads], dg, 0, B, p->Tb, p->Tb);
+    if (do_dec) {
         finish_layer(p, p->layers[d.in_conv], dg, 0, B, p->Tb, p->Tb);
         for (int l = 0; l < d.n; ++l) {
             finish_layer(p, p->layers[d.c1[l]], dg, 0, B, d.T[l], d.T[l]);
@@ -414,7 +430,7 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
     }
 
     // ---- activations.  Inference plans (AVC_PLAN_INFERENCE) keep only what the forward pass touches;
-    // speaker-only plans (AVC_PLAN_SPEAKER_ONLY) only the speaker encoder's buffers.
+    // part plans only their own network's buffers (in a whole plan's allocation order, minus the rest).
     const long Bl = B;
     const long H = p->bh ? 2 : 1;   // a stored [B, C, T] activation takes C / H dword rows per sample (bf16 pairs: half the floats)
     auto alloc_enc = [&](EncNet& e, bool spk) {
@@ -449,13 +465,17 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
             }
         }
     };
-    alloc_enc(p->spk, true);
     const long Cz = dc.c_in, Cd = dc.c_h;
-    p->emb = p->alloc(Bl * dc.c_cond);
-    if (!spk_only) {
+    if (do_spk) {
+        alloc_enc(p->spk, true);
+        p->emb = p->alloc(Bl * dc.c_cond);
+    }
+    if (do_enc) {
         alloc_enc(p->enc, false);
         p->muls = p->alloc(Bl * 2 * Cz * p->Tb);
-        d.z = p->alloc(Bl * (Cz / H) * p->Tb);
+    }
+    if (do_dec) {
+        if (!dec_only || p->bh) d.z = p->alloc(Bl * (Cz / H) * p->Tb);   // (fp32 decoder part plans read the caller's z in place)
         d.cond = p->alloc(Bl * 2 * d.n * 2 * Cd);
         d.y0 = p->alloc(Bl * (Cd / H) * d.T[0]);
         d.out[0] = p->alloc(Bl * (Cd / H) * d.T[0]);
@@ -471,56 +491,71 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
         p->decb = p->alloc(Bl * p->M * p->Tout);
     }
     if (!infer) {
-        p->dmuls = p->alloc(Bl * 2 * Cz * p->Tb);
-        p->demb = p->alloc(Bl * dc.c_cond);
-        p->dz = p->alloc(Bl * Cz * p->Tb);
-        d.dcond = p->alloc(Bl * 2 * d.n * 2 * Cd);
-        p->ddec = p->alloc(Bl * p->M * p->Tout);
-        p->losses = p->alloc(64);
-        p->loss_partial = p->alloc(2 * 1024);
+        if (do_enc) p->dmuls = p->alloc(Bl * 2 * Cz * p->Tb);
+        if (do_spk || do_dec) p->demb = p->alloc(Bl * dc.c_cond);   // (speaker part plans: the caller's d(emb), channel-major)
+        if (do_dec) {
+            p->dz = p->alloc(Bl * Cz * p->Tb);
+            d.dcond = p->alloc(Bl * 2 * d.n * 2 * Cd);
+            p->ddec = p->alloc(Bl * p->M * p->Tout);
+        }
+        if (!part) {
+            p->losses = p->alloc(64);
+            p->loss_partial = p->alloc(2 * 1024);
+        }
         // ---- gradient temporaries (sized for the largest [B, C, T] they ever hold)
         long maxCT = 0;
         auto upd = [&](long c, long t) { maxCT = ((c / H) * t > maxCT) ? (c / H) * t : maxCT; };
-        for (int l = 0; l <= p->spk.n; ++l) upd(p->spk.c.c_h, p->spk.T[l]);
-        for (int l = 0; l <= p->enc.n; ++l) upd(p->enc.c.c_h, p->enc.T[l]);
-        for (int l = 0; l <= d.n; ++l) upd(Cd, d.T[l]);
-        upd(p->M, p->Tout);
-        p->gA = p->alloc(Bl * maxCT);
-        p->gB = p->alloc(Bl * maxCT);
-        p->gC = p->alloc(Bl * maxCT);
-        p->gA2 = p->alloc(Bl * maxCT);
-        p->gB2 = p->alloc(Bl * maxCT);
-        p->gC2 = p->alloc(Bl * maxCT);
-        p->dhA = p->alloc((long)p->spk.c.c_h * Bl);
-        if (p->bh) {
-            p->ddecp = p->alloc(Bl * p->M * p->Tout / 2);
-            p->dmulsp = p->alloc(Bl * Cz * p->Tb);
+        for (int l = 0; l <= p->spk.n && do_spk; ++l) upd(p->spk.c.c_h, p->spk.T[l]);
+        for (int l = 0; l <= p->enc.n && do_enc; ++l) upd(p->enc.c.c_h, p->enc.T[l]);
+        for (int l = 0; l <= d.n && do_dec; ++l) upd(Cd, d.T[l]);
+        if (do_dec) upd(p->M, p->Tout);
+        if (do_enc || do_dec) {   // (the content branch's and the decoder's chains)
+            p->gA = p->alloc(Bl * maxCT);
+            p->gB = p->alloc(Bl * maxCT);
+            p->gC = p->alloc(Bl * maxCT);
         }
+        if (do_spk) {             // (the speaker branch's own set)
+            p->gA2 = p->alloc(Bl * maxCT);
+            p->gB2 = p->alloc(Bl * maxCT);
+            p->gC2 = p->alloc(Bl * maxCT);
+            p->dhA = p->alloc((long)p->spk.c.c_h * Bl);
+        }
+        if (p->bh) {
+            if (do_dec) p->ddecp = p->alloc(Bl * p->M * p->Tout / 2);
+            if (do_enc) p->dmulsp = p->alloc(Bl * Cz * p->Tb);
+        }
+        if (dec_only) p->demb_rm = p->alloc(Bl * dc.c_cond);
     }
 
-    p->named["emb"] = p->emb;
-    p->named["spk_cat"] = p->spk.cat;
-    p->named["spk_out0"] = p->spk.out[0];
-    p->named["spk_pooled"] = p->spk.pooled;
-    p->named["spk_outN"] = p->spk.out[p->spk.n];
-    if (!spk_only) {
+    if (do_spk) {
+        p->named["emb"] = p->emb;
+        p->named["spk_cat"] = p->spk.cat;
+        p->named["spk_out0"] = p->spk.out[0];
+        p->named["spk_pooled"] = p->spk.pooled;
+        p->named["spk_outN"] = p->spk.out[p->spk.n];
+    }
+    if (do_enc) {
         p->named["muls"] = p->muls;
-        p->named["dec"] = p->decb;
-        p->named["z"] = d.z;
-        p->named["cond"] = d.cond;
         p->named["enc_cat"] = p->enc.cat;
         p->named["enc_out0"] = p->enc.out[0];
         p->named["enc_outN"] = p->enc.out[p->enc.n];
+    }
+    if (do_dec) {
+        p->named["dec"] = p->decb;
+        if (d.z >= 0) p->named["z"] = d.z;
+        p->named["cond"] = d.cond;
         p->named["dec_out0"] = d.out[0];
         p->named["dec_outN"] = d.out[d.n];
     }
     if (!infer) {
-        p->named["losses"] = p->losses;
-        p->named["d_dec"] = p->ddec;
-        p->named["d_z"] = p->dz;
-        p->named["d_muls"] = p->dmuls;
-        p->named["d_emb"] = p->demb;
-        p->named["d_cond"] = d.dcond;
+        if (!part) p->named["losses"] = p->losses;
+        if (do_enc) p->named["d_muls"] = p->dmuls;
+        if (do_dec) {
+            p->named["d_dec"] = p->ddec;
+            p->named["d_z"] = p->dz;
+            p->named["d_emb"] = dec_only ? p->demb_rm : p->demb;
+            p->named["d_cond"] = d.dcond;
+        }
     }
 
     // ---- ReLU site table in the reference's forward call order (avc_plan_relu_site).  Pair plans: activation / conv-output tensors
@@ -546,31 +581,35 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
         const int PS = p->bh ? 1 : 0;
         const EncNet& sp = p->spk;
         const int Cs_ = sp.c.c_h;
-        for (int g = 0; g < sp.nb; ++g) conv_site(sp.cat + (long)g * (sp.c.c_bank / H) * sp.T[0], B, sp.c.c_bank, sp.T[0], (long)(sp.CC / H) * sp.T[0], sp.T[0], 1, PS);
-        conv_site(sp.h0, B, Cs_, sp.T[0], (long)(Cs_ / H) * sp.T[0], sp.T[0], 1, PS);
-        for (int l = 0; l < sp.n; ++l) {
-            conv_site(sp.a1[l], B, Cs_, sp.T[l], (long)(Cs_ / H) * sp.T[l], sp.T[l], 1, PS);
-            conv_site(sp.a2[l], B, Cs_, sp.T[l + 1], (long)(Cs_ / H) * sp.T[l + 1], sp.T[l + 1], 1, PS);
-        }
-        for (int l = 0; l < sp.nd; ++l) {  // dense activations are stored channel-major [C][B] fp32; the reference sees [B, C]
-            conv_site(sp.d1[l], B, Cs_, 1, 1, B, 0, 0);
-            conv_site(sp.d2[l], B, Cs_, 1, 1, B, 0, 0);
+        if (do_spk) {
+            for (int g = 0; g < sp.nb; ++g) conv_site(sp.cat + (long)g * (sp.c.c_bank / H) * sp.T[0], B, sp.c.c_bank, sp.T[0], (long)(sp.CC / H) * sp.T[0], sp.T[0], 1, PS);
+            conv_site(sp.h0, B, Cs_, sp.T[0], (long)(Cs_ / H) * sp.T[0], sp.T[0], 1, PS);
+            for (int l = 0; l < sp.n; ++l) {
+                conv_site(sp.a1[l], B, Cs_, sp.T[l], (long)(Cs_ / H) * sp.T[l], sp.T[l], 1, PS);
+                conv_site(sp.a2[l], B, Cs_, sp.T[l + 1], (long)(Cs_ / H) * sp.T[l + 1], sp.T[l + 1], 1, PS);
+            }
+            for (int l = 0; l < sp.nd; ++l) {  // dense activations are stored channel-major [C][B] fp32; the reference sees [B, C]
+                conv_site(sp.d1[l], B, Cs_, 1, 1, B, 0, 0);
+                conv_site(sp.d2[l], B, Cs_, 1, 1, B, 0, 0);
+            }
         }
         const EncNet& en = p->enc;
         const int Ce_ = en.c.c_h;
-        if (!spk_only) {
-        for (int g = 0; g < en.nb; ++g) conv_site(en.cat + (long)g * (en.c.c_bank / H) * en.T[0], B, en.c.c_bank, en.T[0], (long)(en.CC / H) * en.T[0], en.T[0], 1, PS);
-        in_site(en.h0, en.st0, Ce_, en.T[0], -1, 0, PS);
-        for (int l = 0; l < en.n; ++l) {
-            in_site(en.y1[l], en.st1[l], Ce_, en.T[l], -1, 0, PS);
-            in_site(en.y2[l], en.st2[l], Ce_, en.T[l + 1], -1, 0, PS);
+        if (do_enc) {
+            for (int g = 0; g < en.nb; ++g) conv_site(en.cat + (long)g * (en.c.c_bank / H) * en.T[0], B, en.c.c_bank, en.T[0], (long)(en.CC / H) * en.T[0], en.T[0], 1, PS);
+            in_site(en.h0, en.st0, Ce_, en.T[0], -1, 0, PS);
+            for (int l = 0; l < en.n; ++l) {
+                in_site(en.y1[l], en.st1[l], Ce_, en.T[l], -1, 0, PS);
+                in_site(en.y2[l], en.st2[l], Ce_, en.T[l + 1], -1, 0, PS);
+            }
         }
-        const long csb_ = (long)2 * d.n * 2 * Cd;
-        in_site(d.y0, d.st0, (int)Cd, d.T[0], -1, 0, PS);
-        for (int l = 0; l < d.n; ++l) {
-            in_site(d.y1[l], d.st1[l], (int)Cd, d.T[l], d.cond + (long)(2 * l) * 2 * Cd, csb_, PS);
-            in_site(d.y2[l], d.st2[l], (int)Cd, d.T[l + 1], d.cond + (long)(2 * l + 1) * 2 * Cd, csb_, (p->bh && dc.upsample[l] > 1) ? 2 : PS);
-        }
+        if (do_dec) {
+            const long csb_ = (long)2 * d.n * 2 * Cd;
+            in_site(d.y0, d.st0, (int)Cd, d.T[0], -1, 0, PS);
+            for (int l = 0; l < d.n; ++l) {
+                in_site(d.y1[l], d.st1[l], (int)Cd, d.T[l], d.cond + (long)(2 * l) * 2 * Cd, csb_, PS);
+                in_site(d.y2[l], d.st2[l], (int)Cd, d.T[l + 1], d.cond + (long)(2 * l + 1) * 2 * Cd, csb_, (p->bh && dc.upsample[l] > 1) ? 2 : PS);
+            }
         }
     }
 
@@ -1153,8 +1192,10 @@ extern "C" int avc_plan_pack_weights(const avc_plan* p, const float* params, flo
     return 0;
 }
 
+// din: the decoder's inputs of a decoder part plan (NULL: z = the reparameterised latent, emb = the speaker encoder's, both in ws)
 static int forward_impl(const avc_plan* p, const float* params, const float* x, long sxb, long sxc, int sxt,
-                        const float* xc, long scb, long scc, int sct, const float* eps, float* ws, hipStream_t s, bool packed = false) {
+                        const float* xc, long scb, long scc, int sct, const float* eps, float* ws, hipStream_t s, bool packed = false,
+                        const DecIn* din = nullptr) {
     const int B = p->B;
     const bool bh = p->bh;
     const int NV = (int)p->tun.in_pairs_nv;
@@ -1162,10 +1203,12 @@ static int forward_impl(const avc_plan* p, const float* params, const float* x, 
     // optimizer step already (AVC_FWD_WEIGHTS_PACKED)
     if (!packed) RUN(pack_all(p, params, ws, s));
 
-    const bool spk_only = (p->flags & AVC_PLAN_SPEAKER_ONLY) != 0;  // AE.get_speaker_embeddings (model.py:393-395)
+    // part plans run one network: SpeakerEncoder.forward (AE.get_speaker_embeddings, model.py:393-395), ContentEncoder.forward or
+    // Decoder.forward (model.py:265-277 / 301-323 / 347-371) -- the same launches as the whole plan's branch
+    const bool do_spk = has_spk(p->flags), do_enc = has_enc(p->flags), do_dec = has_dec(p->flags);
     // first kernels of the content encoder (conv bank, in_conv, InstanceNorm) on the caller's stream
     auto content_front = [&]() -> int {
-        if (spk_only) return 0;
+        if (!do_enc) return 0;
         const EncNet& e = p->enc;
         const float SL = e.slope;
         const int Cc = e.c.c_h;
@@ -1177,8 +1220,9 @@ static int forward_impl(const avc_plan* p, const float* params, const float* x, 
     };
     // ---------------- speaker encoder (model.py:265-277), concurrent with the content encoder
     const hipStream_t mainS = s;
-    const hipStream_t sideS = fork_side(p, mainS);
-    {
+    const hipStream_t sideS = do_spk ? fork_side(p, mainS) : mainS;
+    if (!do_spk) RUN(content_front());
+    if (do_spk) {
         const hipStream_t s = sideS;
         const EncNet& e = p->spk;
         const float SL = e.slope;
@@ -1231,7 +1275,7 @@ static int forward_impl(const avc_plan* p, const float* params, const float* x, 
     }
 
     // ---------------- content encoder (model.py:301-323)
-    if (!spk_only) {
+    if (do_enc) {
         const EncNet& e = p->enc;
         const float SL = e.slope;
         const int Cc = e.c.c_h;
@@ -1253,16 +1297,29 @@ static int forward_impl(const avc_plan* p, const float* params, const float* x, 
 
     join_side(p, mainS, sideS);
     // ---------------- reparameterisation (model.py:383-384) + decoder (model.py:347-371)
-    if (!spk_only) {
+    if (do_dec) {
         const DecNet& d = p->dec;
         const float SL = d.slope;
         const int Cc = d.c.c_h, Czc = d.c.c_in, Tb = p->Tb;
         const long C = bh ? Cc / 2 : Cc, Cz = bh ? Czc / 2 : Czc;   // rows per sample (pair rows with bh)
-        if (bh) RUN(avc_launch_reparam_fwd_pairs(ws + p->muls, eps, B, Czc, Tb, ws + d.z, s));
-        else RUN(avc_launch_reparam_fwd(ws + p->muls, eps, B, Czc, Tb, ws + d.z, s));
+        // z and emb: the workspace's own, or a decoder part plan's caller tensors read in place (pair plans: z converted to pairs first)
+        const float* zs = ws + d.z;
+        long zsb = Cz * Tb, zsc = Tb;
+        int zst = 1;
+        if (din && !bh) {
+            zs = din->z; zsb = din->szb; zsc = din->szc; zst = din->szt;
+        } else if (din) {
+            RUN(avc_launch_to_pairs(din->z, din->szb, din->szc, din->szt, B, Czc, Tb, ws + d.z, Cz * Tb, Tb, s));
+        } else if (bh) {
+            RUN(avc_launch_reparam_fwd_pairs(ws + p->muls, eps, B, Czc, Tb, ws + d.z, s));
+        } else {
+            RUN(avc_launch_reparam_fwd(ws + p->muls, eps, B, Czc, Tb, ws + d.z, s));
+        }
+        const float* es = din ? din->emb : ws + p->emb;
+        const long esb = din ? din->seb : d.c.c_cond, esc = din ? din->sec : 1;
         const long csb = (long)2 * d.n * 2 * Cc;
         {   // all 2n AdaIN affine Linears as ONE GEMM on emb (they share their input)
-            ConvArgs a = mk_fwd(p, SL, p->layers[d.affine], params, ws, ws + p->emb, 0, 1, d.c.c_cond, 1, B, ws + d.cond, 0, 1, (int)csb, 0);
+            ConvArgs a = mk_fwd(p, SL, p->layers[d.affine], params, ws, es, 0, esc, (int)esb, 1, B, ws + d.cond, 0, 1, (int)csb, 0);
             RUN(avc_launch_conv(a, s, 0, p->tun));
         }
         // The decoder is one serial chain of ~40 small kernels (T_l = 16..128): alone on the GPU it leaves
@@ -1271,10 +1328,10 @@ static int forward_impl(const avc_plan* p, const float* params, const float* x, 
         // a pointer offset.
         // phase 0: in_conv + IN; phases 1 .. 2n: (first conv + AdaIN) / (second conv + AdaIN + residual) of block (ph - 1) / 2; phase 2n + 1: out_conv
         auto dec_phase = [&](int b0, int Bn, hipStream_t s, int ph) -> int {
-            const long oz = (long)b0 * Cz * Tb, ob0 = (long)b0 * C * Tb;
+            const long ob0 = (long)b0 * C * Tb;
             const float* cond = ws + d.cond + (long)b0 * csb;
             if (ph == 0) {
-                ConvArgs a = mk_fwd(p, SL, p->layers[d.in_conv], params, ws, ws + d.z + oz, (long)Cz * Tb, Tb, 1, Bn, Tb, ws + d.y0 + ob0, (long)C * Tb, Tb, 1, 0);
+                ConvArgs a = mk_fwd(p, SL, p->layers[d.in_conv], params, ws, zs + (long)b0 * zsb, zsb, zsc, zst, Bn, Tb, ws + d.y0 + ob0, (long)C * Tb, Tb, 1, 0);
                 RUN(conv_in_fwd(p, a, SL, Bn, Cc, Tb, nullptr, 0, 0, nullptr, 0, 0, ws + d.out[0] + ob0, ws + d.st0, s, B, b0, bh, 0, NV));
                 return 0;
             }
@@ -1327,6 +1384,7 @@ extern "C" int avc_forward(const avc_plan* p, const float* params, const float* 
                            const float* x_cond, long scb, long scc, int sct, const float* eps, float* ws, void* stream) {
     if (!p || !params || !x || !ws) return fail(-1, "avc_forward: null argument");
     if (p->flags & AVC_PLAN_RAGGED) return fail(-8, "avc_forward: ragged plans run through avc_forward_ragged");
+    if (p->flags & AVC_PLAN_DECODER_ONLY) return fail(-8, "avc_forward: decoder part plans run through avc_decoder_forward");
     if (!x_cond) {
         x_cond = x; scb = sxb; scc = sxc; sct = sxt;
     }
@@ -1337,6 +1395,7 @@ extern "C" int avc_forward_ex(const avc_plan* p, const float* params, const floa
                               const float* x_cond, long scb, long scc, int sct, const float* eps, float* ws, int flags, void* stream) {
     if (!p || !params || !x || !ws) return fail(-1, "avc_forward_ex: null argument");
     if (p->flags & AVC_PLAN_RAGGED) return fail(-8, "avc_forward_ex: ragged plans run through avc_forward_ragged");
+    if (p->flags & AVC_PLAN_DECODER_ONLY) return fail(-8, "avc_forward_ex: decoder part plans run through avc_decoder_forward");
     if (flags & ~AVC_FWD_WEIGHTS_PACKED) return fail(-1, "avc_forward_ex: unknown flag");
     if (!x_cond) {
         x_cond = x; scb = sxb; scc = sxc; sct = sxt;
@@ -1344,8 +1403,21 @@ extern "C" int avc_forward_ex(const avc_plan* p, const float* params, const floa
     return forward_impl(p, params, x, sxb, sxc, sxt, x_cond, scb, scc, sct, eps, ws, (hipStream_t)stream, (flags & AVC_FWD_WEIGHTS_PACKED) != 0);
 }
 
+// Decoder.forward(z, cond) (model.py:347-371) on a decoder part plan: the caller's z / emb in place of the latent and the embedding
+extern "C" int avc_decoder_forward(const avc_plan* p, const float* params, const float* z, long szb, long szc, int szt, const float* emb,
+                                   long seb, long sec, float* ws, int flags, void* stream) {
+    if (!p || !params || !z || !emb || !ws) return fail(-1, "avc_decoder_forward: null argument");
+    if (!(p->flags & AVC_PLAN_DECODER_ONLY)) return fail(-8, "avc_decoder_forward: the plan was not created with AVC_PLAN_DECODER_ONLY");
+    if (flags & ~AVC_FWD_WEIGHTS_PACKED) return fail(-1, "avc_decoder_forward: unknown flag");
+    const DecIn din = {z, szb, szc, szt, emb, seb, sec};
+    return forward_impl(p, params, nullptr, 0, 0, 0, nullptr, 0, 0, 0, nullptr, ws, (hipStream_t)stream, (flags & AVC_FWD_WEIGHTS_PACKED) != 0,
+                        &din);
+}
+
 extern "C" int avc_loss(const avc_plan* p, const float* x, long sxb, long sxc, int sxt, float lambda_rec, float* ws,
                         void* stream) {
+    if (!p) return fail(-1, "avc_loss: null plan");
+    if (p->flags & AVC_PLAN_PARTS) return fail(-8, "avc_loss: part plans have no loss (the caller's autograd takes the losses of solver.py:84-88)");
     if (p->flags & AVC_PLAN_INFERENCE) return fail(-8, "avc_loss: the plan was created with AVC_PLAN_INFERENCE");
     if (p->Tout != p->T) return fail(-7, "avc_loss: L1Loss needs dec and x of equal length (T % 8 == 0 for the stock config)");
     RUN(avc_launch_loss(ws + p->decb, x, sxb, sxc, sxt, p->B, p->M, p->T, ws + p->muls, p->dec.c.c_in, p->Tb, lambda_rec,
@@ -1386,7 +1458,7 @@ static int enc_back_front(BwdCtx& c, const EncNet& e, const float* x, long sxb, 
 int avc_backward_impl(const avc_plan* p, const float* params, const float* x, long sxb, long sxc, int sxt, const float* xc,
                       long scb, long scc, int sct, const float* eps, const float* d_dec, const float* d_muls_up,
                       const float* d_emb_up, float lambda_kl, float* grads, float* ws, hipStream_t s, bool dry,
-                      long* slab_need) {
+                      long* slab_need, const DecIn* din) {
     BwdCtx c;
     c.p = p; c.params = params; c.grads = grads; c.ws = ws; c.s = s; c.dry = dry; c.slab_used = 0;
     if (!dry) avc_prof_mark(0, s);
@@ -1403,9 +1475,12 @@ int avc_backward_impl(const avc_plan* p, const float* params, const float* x, lo
     float* dyA = nullptr;
     float* dyB = nullptr;
     auto rot = [&]() { float* t = gA; gA = gC; gC = t; };
+    // part plans: one network's backward (a decoder part plan's z / emb are the caller's: din)
+    const bool do_spk = has_spk(p->flags), do_enc = has_enc(p->flags), do_dec = has_dec(p->flags);
+    const bool dec_only = (p->flags & AVC_PLAN_DECODER_ONLY) != 0;
 
     // ---------------- decoder
-    {
+    if (do_dec) {
         const DecNet& d = p->dec;
         const float SL = d.slope;
         const int Cc = d.c.c_h, Czc = d.c.c_in, Tb = p->Tb, To = p->Tout;
@@ -1413,6 +1488,13 @@ int avc_backward_impl(const avc_plan* p, const float* params, const float* x, lo
         const long Mr = bh ? p->M / 2 : p->M;
         const long csb = (long)2 * d.n * 2 * Cc;
         const float* ddec = d_dec ? d_dec : ws + p->ddec;
+        // the in_conv's input z and the affine GEMM's input emb, as the forward pass read them
+        const float* zs = ws + d.z;
+        long zsb = Cz * Tb, zsc = Tb;
+        int zst = 1;
+        if (din && !bh) { zs = din->z; zsb = din->szb; zsc = din->szc; zst = din->szt; }
+        const float* es = din ? din->emb : ws + p->emb;
+        const long esb = din ? din->seb : d.c.c_cond, esc = din ? din->sec : 1;
         if (bh) {   // the conv launches read pair operands: d(dec) (fp32: written by avc_loss or handed in by the autograd seam) -> pairs
             if (!dry) RUN(avc_launch_to_pairs(ddec, (long)p->M * To, To, 1, B, p->M, To, ws + p->ddecp, Mr * To, To, s));
             ddec = ws + p->ddecp;
@@ -1515,7 +1597,7 @@ int avc_backward_impl(const avc_plan* p, const float* params, const float* x, lo
         const int early = p->tun.dec_wgrad_flush;
         auto rec_phase = [&](int ph) -> int {   // (the order of the records is the order of round 3: out_conv, blocks n-1 .. 0 (second, first conv), in_conv)
             if (ph == 0) return wgrad_layer(c, Lo, ws + d.out[d.n], (long)C * To, To, 1, ddec, Mr * To, To, 1, 1, B, To, To);
-            if (ph == 2 * d.n + 1) return wgrad_layer(c, Li, ws + d.z, (long)Cz * Tb, Tb, 1, dy0, (long)C * Tb, Tb, 1, 1, B, Tb, Tb);
+            if (ph == 2 * d.n + 1) return wgrad_layer(c, Li, zs, zsb, zsc, zst, dy0, (long)C * Tb, Tb, 1, 1, B, Tb, Tb);
             const int l = d.n - 1 - (ph - 1) / 2;
             const int Ti = d.T[l], T2 = d.T[l + 1], up = d.c.upsample[l];
             if ((ph - 1) % 2 == 0) {
@@ -1553,7 +1635,7 @@ int avc_backward_impl(const avc_plan* p, const float* params, const float* x, lo
         }
         // affine Linears: dW/db from (emb, dcond), d(emb) = W^T dcond (+ upstream)
         const LayerP& La = p->layers[d.affine];
-        RUN(wgrad_layer(c, La, ws + p->emb, 0, 1, d.c.c_cond, ws + d.dcond, 0, 1, (int)csb, 1, 1, B, B));
+        RUN(wgrad_layer(c, La, es, 0, esc, (int)esb, ws + d.dcond, 0, 1, (int)csb, 1, 1, B, B));
         {
             // d(emb)[i][b] = sum_o W[o][i] * dcond[b][o]: a 128 x B output with K = 2n*2C = 3072.  As a dgrad
             // launch that is 8 workgroups walking 96 chunks one after the other (206 us on the critical
@@ -1576,10 +1658,16 @@ int avc_backward_impl(const avc_plan* p, const float* params, const float* x, lo
                 w.db = nullptr;
                 RUN(avc_launch_wgrad_batch(&w, 1, s, p->tun.wgrad_ablation));
                 if (d_emb_up) RUN(avc_launch_add_transposed(ws + p->demb, d_emb_up, B, d.c.c_cond, s));
+                if (dec_only) RUN(avc_launch_transpose(ws + p->demb_rm, ws + p->demb, d.c.c_cond, B, s));   // -> the caller's row-major [B, c_cond]
             }
         }
+        if (dec_only) {   // no latent step and no speaker branch to hide the decoder's weight gradients under: they go out now
+            c.hold = false;
+            RUN(flush_wgrads(c));
+            if (!dry && p->side_state == 1) hipEventRecord(p->ev_dec_grads, c.wstream);
+        }
         // latent: KL term + reparameterisation (solver.py:86, model.py:384)
-        if (!dry) {
+        if (!dry && !dec_only) {
             float lk = lambda_kl / (float)((long)B * Czc * Tb);
             RUN(avc_launch_latent_bwd(ws + p->muls, eps, ws + p->dz, d_muls_up, B, Czc, Tb, lk, ws + p->dmuls, s));
             if (bh) RUN(avc_launch_to_pairs(ws + p->dmuls, (long)2 * Czc * Tb, Tb, 1, B, 2 * Czc, Tb, ws + p->dmulsp, (long)Czc * Tb, Tb, s));
@@ -1648,10 +1736,24 @@ int avc_backward_impl(const avc_plan* p, const float* params, const float* x, lo
         return 0;
     };
 
+    if (!do_dec && do_enc && !dry) {   // content part plan: d(muls) = upstream + the KL term (solver.py:86), no z
+        const int Czc = p->dec.c.c_in, Tb = p->Tb;
+        float lk = lambda_kl / (float)((long)B * Czc * Tb);
+        RUN(avc_launch_latent_bwd(ws + p->muls, nullptr, nullptr, d_muls_up, B, Czc, Tb, lk, ws + p->dmuls, s));
+        if (bh) RUN(avc_launch_to_pairs(ws + p->dmuls, (long)2 * Czc * Tb, Tb, 1, B, 2 * Czc, Tb, ws + p->dmulsp, (long)Czc * Tb, Tb, s));
+    }
+    if (!do_dec && do_spk && !dry)   // speaker part plan: the caller's d(emb) [B, c_out] -> the dense stack's channel-major operand
+        RUN(avc_launch_transpose(ws + p->demb, d_emb_up, B, p->spk.c.c_out, s));
+
     // ---------------- speaker encoder (side stream, own temporaries: concurrent with the content encoder)
     const hipStream_t mainS = s;
-    const hipStream_t sideS = use_side ? fork_side(p, mainS) : mainS;
-    {
+    const hipStream_t sideS = (use_side && do_spk) ? fork_side(p, mainS) : mainS;
+    if (!do_spk && do_enc) {   // content part plan: its branch alone, on the caller's stream
+        c.s = mainS;
+        c.wstream = overlap ? p->wstream[0] : mainS;
+        RUN(content_branch());
+    }
+    if (do_spk) {
         const hipStream_t s = sideS;
         c.s = sideS;
         float* gA = ws + p->gA2;
@@ -1732,7 +1834,7 @@ int avc_backward_impl(const avc_plan* p, const float* params, const float* x, lo
             hipEventRecord(p->ev_dense, sideS);
             hipStreamWaitEvent(mainS, p->ev_dense, 0);
         }
-        RUN(content_branch());
+        if (do_enc) RUN(content_branch());
         if (!dry && (p->tun.dbg_streams & 4) && sideS != mainS) {   // (diagnostic: the speaker's conv chain starts behind the content chain)
             hipEventRecord(p->ev_join, mainS);
             hipStreamWaitEvent(sideS, p->ev_join, 0);
@@ -1802,12 +1904,31 @@ extern "C" int avc_backward(const avc_plan* p, const float* params, const float*
                             const float* d_muls_up, const float* d_emb_up, float lambda_kl, float* grads, float* ws,
                             void* stream) {
     if (!p || !params || !x || !ws || !grads) return fail(-1, "avc_backward: null argument");
+    if ((p->flags & AVC_PLAN_PARTS) && (p->flags & AVC_PLAN_INFERENCE))
+        return fail(-8, "avc_backward: a part plan needs AVC_PLAN_PART_GRADS for its backward (no gradient buffers)");
     if (p->flags & AVC_PLAN_INFERENCE) return fail(-8, "avc_backward: the plan was created with AVC_PLAN_INFERENCE (no gradient buffers)");
+    if (p->flags & AVC_PLAN_DECODER_ONLY) return fail(-8, "avc_backward: decoder part plans run through avc_decoder_backward");
+    if ((p->flags & AVC_PLAN_CONTENT_ONLY) && (d_dec || d_emb_up))
+        return fail(-1, "avc_backward: a content part plan takes d_muls_up only (d_dec and d_emb_up must be NULL)");
+    if ((p->flags & AVC_PLAN_SPEAKER_ONLY) && (d_dec || d_muls_up || !d_emb_up))
+        return fail(-1, "avc_backward: a speaker part plan takes d_emb_up only (d_dec and d_muls_up must be NULL)");
     if (!x_cond) {
         x_cond = x; scb = sxb; scc = sxc; sct = sxt;
     }
     return avc_backward_impl(p, params, x, sxb, sxc, sxt, x_cond, scb, scc, sct, eps, d_dec, d_muls_up, d_emb_up, lambda_kl,
                              grads, ws, (hipStream_t)stream, false, nullptr);
+}
+
+// autograd of Decoder.forward (model.py:347-371) on a decoder part plan with AVC_PLAN_PART_GRADS: the decoder's parameter gradients,
+// ws["d_z"] and ws["d_emb"] (row-major) from d(dec); z / emb / params as handed to the avc_decoder_forward this pass follows
+extern "C" int avc_decoder_backward(const avc_plan* p, const float* params, const float* z, long szb, long szc, int szt, const float* emb,
+                                    long seb, long sec, const float* d_dec, float* grads, float* ws, void* stream) {
+    if (!p || !params || !z || !emb || !ws || !grads) return fail(-1, "avc_decoder_backward: null argument");
+    if (!(p->flags & AVC_PLAN_DECODER_ONLY)) return fail(-8, "avc_decoder_backward: the plan was not created with AVC_PLAN_DECODER_ONLY");
+    if (p->flags & AVC_PLAN_INFERENCE) return fail(-8, "avc_decoder_backward: the plan was created without AVC_PLAN_PART_GRADS (no gradient buffers)");
+    const DecIn din = {z, szb, szc, szt, emb, seb, sec};
+    return avc_backward_impl(p, params, nullptr, 0, 0, 0, nullptr, 0, 0, 0, nullptr, d_dec, nullptr, nullptr, 0.f, grads, ws, (hipStream_t)stream,
+                             false, nullptr, &din);
 }
 
 

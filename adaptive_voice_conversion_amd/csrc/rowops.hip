@@ -357,6 +357,15 @@ __global__ void __launch_bounds__(AVC_THREADS) add_transposed_kernel(float* dst,
     dst[e] += src[(long)b * C + c];
 }
 
+// dst[c][r] = src[r][c]: an [R][C] matrix to [C][R] (part plans: d(emb) between the caller's row-major [B, c_cond] and the channel-major
+// layout of the dense stack / the affine GEMM)
+__global__ void __launch_bounds__(AVC_THREADS) transpose_kernel(float* dst, const float* src, int R, int C) {
+    int e = blockIdx.x * AVC_THREADS + threadIdx.x;
+    if (e >= R * C) return;
+    int c = e / R, r = e - c * R;
+    dst[e] = src[(long)r * C + c];
+}
+
 // AdaptiveAvgPool1d(1) (model.py:273): in [B,C,T] -> out[c*B + b]  (channel-major for the dense stack)
 __global__ void __launch_bounds__(AVC_THREADS) timepool_fwd_kernel(const float* in, int B, int C, int T, float* out) {
     int r = blockIdx.x * AVC_THREADS + threadIdx.x;
@@ -658,6 +667,12 @@ int avc_launch_gather_segments(const float* corpus, long n_rows, int M, const lo
 int avc_launch_add_transposed(float* dst, const float* src, int B, int C, hipStream_t s) {
     ProfScope ps(AVC_K_MISC, 0.0, 0.0, s);
     hipLaunchKernelGGL(add_transposed_kernel, dim3(avc_cdiv(B * C, AVC_THREADS)), dim3(AVC_THREADS), 0, s, dst, src, B, C);
+    return (int)hipGetLastError();
+}
+int avc_launch_transpose(float* dst, const float* src, int R, int C, hipStream_t s) {
+    if (R < 1 || C < 1) return -1;
+    ProfScope ps(AVC_K_MISC, 0.0, 8.0 * (double)R * C, s);
+    hipLaunchKernelGGL(transpose_kernel, dim3(avc_cdiv(R * C, AVC_THREADS)), dim3(AVC_THREADS), 0, s, dst, src, R, C);
     return (int)hipGetLastError();
 }
 int avc_launch_timepool_fwd(const float* in, int B, int C, int T, float* out, hipStream_t s) {

@@ -99,6 +99,10 @@ class Plan:
     """One (B, T, T_cond) launch plan.  ``lib`` defaults to the gfx950 library;
     tests may inject the CPU lane-level simulation build instead."""
 
+    MODES = {"train": 0, "inference": _lib.PLAN_INFERENCE, "speaker": _lib.PLAN_INFERENCE | _lib.PLAN_SPEAKER_ONLY,
+             "content": _lib.PLAN_INFERENCE | _lib.PLAN_CONTENT_ONLY, "decoder": _lib.PLAN_INFERENCE | _lib.PLAN_DECODER_ONLY,
+             "speaker_train": _lib.PLAN_SPEAKER_ONLY | _lib.PLAN_PART_GRADS, "content_train": _lib.PLAN_CONTENT_ONLY | _lib.PLAN_PART_GRADS,
+             "decoder_train": _lib.PLAN_DECODER_ONLY | _lib.PLAN_PART_GRADS}
     COMPUTE = {"fp32": 0, "float32": 0, "f32": 0, "fp32x3": 0, "f32x3": 0, "bf16": 3, "bfloat16": 3, "bf16s": 3, "bf16_storage": 3,
                "bf16r": 1, "bf16_operands": 1}
 
@@ -112,7 +116,10 @@ class Plan:
         "fp32x3" = fp32-accurate products from three bf16 terms per operand on the bf16 matrix core for the big k = 5 convs and the
         whole-chunk weight gradients (opt-in; csrc/conv_x3.hip), exact fp32 everywhere else.
         mode: "train" (forward + loss + backward), "inference" (forward only: the workspace holds no gradient,
-        slab or dy buffers) or "speaker" (only the speaker encoder runs, AE.get_speaker_embeddings).
+        slab or dy buffers) or "speaker" (only the speaker encoder runs, AE.get_speaker_embeddings); part plans of ONE network
+        (SpeakerEncoder / ContentEncoder / Decoder.forward, model.py:265-277 / 301-323 / 347-371): "speaker", "content" and "decoder"
+        run forward only, "speaker_train", "content_train" and "decoder_train" also their backward.  A decoder plan takes
+        T = the latent length Tb of its input z and runs through ``decoder_forward`` / ``decoder_backward``.
         device: the plan's helper streams are created on it (default: the current device).
         tuning: {avc_tuning field: value} overrides of the launch heuristics / diagnostic switches the plan captures
         (A/B measurements and tests; include/avc_hip.h).  The library has no process-wide knobs."""
@@ -120,7 +127,7 @@ class Plan:
         self.cfg = cfg_from_dict(config)
         self.B, self.T, self.T_cond = int(B), int(T), int(T_cond or T)
         self.mode = mode
-        flags = {"train": 0, "inference": _lib.PLAN_INFERENCE, "speaker": _lib.PLAN_INFERENCE | _lib.PLAN_SPEAKER_ONLY}[mode]
+        flags = self.MODES[mode]
         h = ctypes.c_void_p()
         dev = torch.device(device) if device is not None else None
         key = str(compute_dtype).lower()
@@ -275,6 +282,21 @@ class Plan:
             self._chk(self.lib.avc_backward(self.h, _ptr(params), _ptr(x), x.stride(0), x.stride(1), x.stride(2), _ptr(xc),
                                             xc.stride(0), xc.stride(1), xc.stride(2), _ptr(eps), _ptr(d_dec), _ptr(d_muls),
                                             _ptr(d_emb), float(lambda_kl), _ptr(grads), _ptr(ws), _stream(ws)))
+
+
+    def decoder_forward(self, params, z, emb, ws, weights_packed=False):
+        """Decoder.forward(z, emb) (model.py:347-371) on a decoder plan: z [B, c_in, Tb] and emb [B, c_cond] (fp32, any strides) are
+        read in place; the result is ws["dec"]."""
+        with _on(ws):
+            self._chk(self.lib.avc_decoder_forward(self.h, _ptr(params), _ptr(z), z.stride(0), z.stride(1), z.stride(2), _ptr(emb), emb.stride(0),
+                                                   emb.stride(1), _ptr(ws), _lib.FWD_WEIGHTS_PACKED if weights_packed else 0, _stream(ws)))
+
+    def decoder_backward(self, params, z, emb, grads, ws, d_dec=None):
+        """Its backward ("decoder_train" plans, after decoder_forward with the same z / emb): the decoder's range of ``grads``,
+        ws["d_z"] [B, c_in, Tb] and ws["d_emb"] [B, c_cond].  d_dec: [B, M, Tout] contiguous (None = ws["d_dec"])."""
+        with _on(ws):
+            self._chk(self.lib.avc_decoder_backward(self.h, _ptr(params), _ptr(z), z.stride(0), z.stride(1), z.stride(2), _ptr(emb), emb.stride(0),
+                                                    emb.stride(1), _ptr(d_dec), _ptr(grads), _ptr(ws), _stream(ws)))
 
 
 class RaggedPlan:

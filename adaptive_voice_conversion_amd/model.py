@@ -9,8 +9,13 @@ methods ``forward / inference / get_speaker_embeddings``.
 
 What is different: no torch op computes anything.  All parameters alias ONE flat
 fp32 buffer (and all gradients another) laid out as the C plan dictates, and
-forward/backward are single calls into the gfx950 engine.
+forward/backward are single calls into the gfx950 engine.  The three sub-modules
+are callable with the reference's signatures (``speaker_encoder(x)``,
+``content_encoder(x)``, ``decoder(z, cond)``); each runs a part plan of the engine
+through its owning ``AE``.
 """
+import weakref
+
 import torch
 import torch.nn as nn
 
@@ -22,10 +27,19 @@ def _bank_kernels(c):
 
 
 class _ParamHolder(nn.Module):
-    """A network of the reference reduced to its parameter containers."""
+    """A network of the reference: its parameter containers, and a ``forward`` that runs the engine's part plan of this network
+    through the owning ``AE`` (the plans, workspaces and the flat parameter buffer are the AE's)."""
 
     def extra_repr(self):
         return "parameters only; compute runs in libavc_hip.so"
+
+    def _owner(self):
+        ref = self.__dict__.get("_ae_ref")   # a weakref, set by AE.__init__: NOT a registered sub-module (state_dict / parameters unchanged)
+        ae = ref() if ref is not None else None
+        if ae is None:
+            raise RuntimeError(f"{type(self).__name__} computes through the AE that owns it (its parameters alias the AE's flat buffer); "
+                               "construct it as part of AE(config)")
+        return ae
 
 
 class SpeakerEncoder(_ParamHolder):
@@ -44,6 +58,10 @@ class SpeakerEncoder(_ParamHolder):
         self.second_dense_layers = nn.ModuleList(nn.Linear(c_h, c_h) for _ in range(n_dense_blocks))
         self.output_layer = nn.Linear(c_h, c_out)
 
+    def forward(self, x):
+        """model.py:265-277: x [B, M, T] -> emb [B, c_out]."""
+        return self._owner()._speaker_forward(x)
+
 
 class ContentEncoder(_ParamHolder):
     """Parameter layout of model.py:279-299."""
@@ -60,6 +78,10 @@ class ContentEncoder(_ParamHolder):
         self.mean_layer = nn.Conv1d(c_h, c_out, kernel_size=1)
         self.std_layer = nn.Conv1d(c_h, c_out, kernel_size=1)
 
+    def forward(self, x):
+        """model.py:301-323: x [B, M, T] -> (mu, log_sigma), [B, c_out, Tb] each."""
+        return self._owner()._content_forward(x)
+
 
 class Decoder(_ParamHolder):
     """Parameter layout of model.py:325-345 (sn=False only)."""
@@ -72,6 +94,10 @@ class Decoder(_ParamHolder):
             nn.Conv1d(c_h, c_h * up, kernel_size=kernel_size) for _, up in zip(range(n_conv_blocks), upsample))
         self.conv_affine_layers = nn.ModuleList(nn.Linear(c_cond, c_h * 2) for _ in range(n_conv_blocks * 2))
         self.out_conv_layer = nn.Conv1d(c_h, c_out, kernel_size=1)
+
+    def forward(self, z, cond):
+        """model.py:347-371: z [B, c_in, Tb], cond [B, c_cond] -> dec [B, c_out, Tb * prod(upsample)]."""
+        return self._owner()._decoder_forward(z, cond)
 
 
 class _Token:
@@ -199,6 +225,108 @@ class _AEFunction(torch.autograd.Function):
         return (None, None, None) + grads
 
 
+class _PartFunction(torch.autograd.Function):
+    """Shared steps of the three sub-module seams (the pattern of _AEFunction): a part plan of the training flavour ("*_train") from the
+    AE's plan cache, a private workspace when the cached one still holds a pending backward's activations, and the gradients of THIS
+    network's parameters only (the part backward writes exactly that range of the flat gradient buffer)."""
+
+    @staticmethod
+    def _begin(ctx, ae, mode, B, T, device):
+        entry = ae._entry(mode, B, T, T, device)
+        plan, ws = entry.plan, entry.ws
+        if entry.busy():
+            ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=device)   # private to this forward
+        token = _Token()
+        if ws is entry.ws:
+            entry.pending = weakref.ref(token)
+        ctx.ae, ctx.plan, ctx.ws, ctx.token = ae, plan, ws, token
+        return plan, ws
+
+    @staticmethod
+    def _check(ctx):
+        if ctx.token.done:
+            raise RuntimeError("AE: backward through the same forward twice (the engine keeps one set of saved activations)")
+        if ctx.plan.h is None:
+            raise RuntimeError("AE: the launch plan of this forward was released (model moved / cache cleared) before backward()")
+
+    @staticmethod
+    def _grads(ctx, g, part):
+        ctx.token.done = True
+        lo, hi = ctx.ae._part_index[part]
+        return tuple(g[off:off + n].view(shape) for off, n, shape in ctx.ae._layout[lo:hi])
+
+
+class _SpeakerFunction(_PartFunction):
+    """SpeakerEncoder.forward (model.py:265-277) with autograd: x gets no gradient, as in AE.forward."""
+
+    @staticmethod
+    def forward(ctx, ae, x, *params):
+        B, T = x.shape[0], x.shape[2]
+        plan, ws = _PartFunction._begin(ctx, ae, "speaker_train", B, T, x.device)
+        plan.forward(ae._flat, x, None, None, ws)
+        ctx.save_for_backward(x)
+        return plan.view(ws, "emb", (B, ae._c_emb)).clone()
+
+    @staticmethod
+    def backward(ctx, d_emb):
+        _PartFunction._check(ctx)
+        x, = ctx.saved_tensors
+        g = torch.empty_like(ctx.ae._flat)
+        ctx.plan.backward(ctx.ae._flat, x, None, None, g, ctx.ws, d_emb=d_emb.contiguous().float())
+        return (None, None) + _PartFunction._grads(ctx, g, "speaker")
+
+
+class _ContentFunction(_PartFunction):
+    """ContentEncoder.forward (model.py:301-323) with autograd: x gets no gradient, as in AE.forward."""
+
+    @staticmethod
+    def forward(ctx, ae, x, *params):
+        B, T = x.shape[0], x.shape[2]
+        plan, ws = _PartFunction._begin(ctx, ae, "content_train", B, T, x.device)
+        plan.forward(ae._flat, x, None, None, ws)
+        ctx.save_for_backward(x)
+        muls = plan.view(ws, "muls", (B, 2 * ae._c_lat, plan.latent_len))
+        return muls[:, :ae._c_lat].clone(), muls[:, ae._c_lat:].clone()
+
+    @staticmethod
+    def backward(ctx, d_mu, d_ls):
+        _PartFunction._check(ctx)
+        x, = ctx.saved_tensors
+        ae, plan = ctx.ae, ctx.plan
+        C = ae._c_lat
+        d_muls = torch.zeros(x.shape[0], 2 * C, plan.latent_len, device=x.device, dtype=torch.float32)
+        if d_mu is not None:
+            d_muls[:, :C] = d_mu
+        if d_ls is not None:
+            d_muls[:, C:] = d_ls
+        g = torch.empty_like(ae._flat)
+        plan.backward(ae._flat, x, None, None, g, ctx.ws, d_muls=d_muls, lambda_kl=0.0)
+        return (None, None) + _PartFunction._grads(ctx, g, "content")
+
+
+class _DecoderFunction(_PartFunction):
+    """Decoder.forward(z, cond) (model.py:347-371) with autograd: gradients for z, cond and the decoder's parameters."""
+
+    @staticmethod
+    def forward(ctx, ae, z, cond, *params):
+        plan, ws = _PartFunction._begin(ctx, ae, "decoder_train", z.shape[0], z.shape[2], z.device)
+        plan.decoder_forward(ae._flat, z, cond, ws)
+        ctx.save_for_backward(z, cond)   # (the engine reads them again in place: the in_conv's and the affine GEMM's weight gradients)
+        return plan.view(ws, "dec", (z.shape[0], ae._n_mels, plan.out_len)).clone()
+
+    @staticmethod
+    def backward(ctx, d_dec):
+        _PartFunction._check(ctx)
+        z, cond = ctx.saved_tensors
+        ae, plan, ws = ctx.ae, ctx.plan, ctx.ws
+        B = z.shape[0]
+        g = torch.empty_like(ae._flat)
+        plan.decoder_backward(ae._flat, z, cond, g, ws, d_dec=d_dec.contiguous().float())
+        dz = plan.view(ws, "d_z", (B, ae._c_lat, plan.latent_len)).clone() if ctx.needs_input_grad[1] else None
+        dcond = plan.view(ws, "d_emb", (B, ae._c_emb)).clone() if ctx.needs_input_grad[2] else None
+        return (None, dz, dcond) + _PartFunction._grads(ctx, g, "decoder")
+
+
 class AE(nn.Module):
     """model.py:373-395."""
 
@@ -216,6 +344,9 @@ class AE(nn.Module):
         self.speaker_encoder = SpeakerEncoder(**config["SpeakerEncoder"])
         self.content_encoder = ContentEncoder(**config["ContentEncoder"])
         self.decoder = Decoder(**config["Decoder"])
+        # each network reaches this AE through a weak reference in its __dict__: not a registered sub-module, no reference cycle
+        for m in (self.speaker_encoder, self.content_encoder, self.decoder):
+            object.__setattr__(m, "_ae_ref", weakref.ref(self))
         self._n_mels = int(config["ContentEncoder"]["c_in"])
         self._c_lat = int(config["ContentEncoder"]["c_out"])
         self._c_emb = int(config["SpeakerEncoder"]["c_out"])
@@ -224,6 +355,9 @@ class AE(nn.Module):
         for p in self.parameters():
             self._layout.append((off, p.numel(), tuple(p.shape)))
             off += (p.numel() + 3) // 4 * 4
+        # [lo, hi) of each network's entries in _layout (registration order: speaker encoder, content encoder, decoder)
+        n_spk, n_enc = len(list(self.speaker_encoder.parameters())), len(list(self.content_encoder.parameters()))
+        self._part_index = {"speaker": (0, n_spk), "content": (n_spk, n_spk + n_enc), "decoder": (n_spk + n_enc, len(self._layout))}
         self._flat = torch.zeros(off, dtype=torch.float32)
         with torch.no_grad():
             for (o, n, _), p in zip(self._layout, self.parameters()):
@@ -232,7 +366,9 @@ class AE(nn.Module):
         self._bump = 0
         self._alias()
         # train: the regular batch + the short last batch of an epoch; inference / speaker: a few recent shapes
-        self._plans = _PlanCache({"train": 2, "inference": 8, "speaker": 4})
+        self._plans = _PlanCache({"train": 2, "inference": 8, "speaker": 4,
+                                  # sub-module calls (part plans): forward-only / with backward
+                                  "content": 4, "decoder": 4, "speaker_train": 2, "content_train": 2, "decoder_train": 2})
         self._ragged = {}   # (lengths, device) -> (RaggedPlan, None), a few most recent
         self._ragged_ws = None   # the one workspace they share
         self.last_ragged_compute = None
@@ -303,7 +439,7 @@ class AE(nn.Module):
         ``inference_compute_dtype`` in the config overrides it (e.g. "bf16s": pair storage for uniform inference batches, faster, its own
         rounding points)."""
         cd = str(self.compute_dtype).lower()
-        if mode != "train" and cd in ("bf16", "bfloat16"):
+        if not (mode == "train" or mode.endswith("_train")) and cd in ("bf16", "bfloat16"):   # (sub-module part plans: "*_train" train)
             return (self.config.get("inference_compute_dtype") if isinstance(self.config, dict) else None) or "bf16r"
         return self.compute_dtype
 
@@ -395,6 +531,43 @@ class AE(nn.Module):
         xc = torch.cat([self._prep(t).to(dev) for t in x_conds]).contiguous()
         plan.forward(self._flat, x, xc, ws)
         return [o.clone() for o in plan.outputs(ws)]
+
+    # ---- the three networks called on their own (SpeakerEncoder / ContentEncoder / Decoder.forward) --------
+    def _part_grad(self, part, *inputs):
+        lo, hi = self._part_index[part]
+        return torch.is_grad_enabled() and (any(p.requires_grad for p in list(self.parameters())[lo:hi]) or
+                                            any(t.requires_grad for t in inputs))
+
+    def _speaker_forward(self, x):
+        x = self._prep(x)
+        self._check_device(x)
+        if self._part_grad("speaker"):
+            return _SpeakerFunction.apply(self, x.detach(), *self.speaker_encoder.parameters())
+        plan, ws = self._plan(x.shape[0], x.shape[2], x.shape[2], x.device, "speaker")
+        plan.forward(self._flat, x, None, None, ws)
+        return plan.view(ws, "emb", (x.shape[0], self._c_emb)).clone()
+
+    def _content_forward(self, x):
+        x = self._prep(x)
+        self._check_device(x)
+        if self._part_grad("content"):
+            return _ContentFunction.apply(self, x.detach(), *self.content_encoder.parameters())
+        plan, ws = self._plan(x.shape[0], x.shape[2], x.shape[2], x.device, "content")
+        plan.forward(self._flat, x, None, None, ws)
+        muls = plan.view(ws, "muls", (x.shape[0], 2 * self._c_lat, plan.latent_len))
+        return muls[:, :self._c_lat].clone(), muls[:, self._c_lat:].clone()
+
+    def _decoder_forward(self, z, cond):
+        z, cond = self._prep(z), self._prep(cond)
+        self._check_device(z)
+        self._check_device(cond)
+        if z.dim() != 3 or z.shape[1] != self._c_lat or cond.dim() != 2 or cond.shape != (z.shape[0], self._c_emb):
+            raise ValueError(f"Decoder: z must be [B, {self._c_lat}, Tb] and cond [B, {self._c_emb}], got {tuple(z.shape)} and {tuple(cond.shape)}")
+        if self._part_grad("decoder", z, cond):
+            return _DecoderFunction.apply(self, z, cond, *self.decoder.parameters())
+        plan, ws = self._plan(z.shape[0], z.shape[2], z.shape[2], z.device, "decoder")
+        plan.decoder_forward(self._flat, z, cond, ws)
+        return plan.view(ws, "dec", (z.shape[0], self._n_mels, plan.out_len)).clone()
 
     def get_speaker_embeddings(self, x):
         """model.py:393-395: only the speaker encoder runs (a speaker-only plan)."""

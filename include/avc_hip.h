@@ -88,10 +88,29 @@ const char* avc_last_error(void);
  * reflect pad is not smaller than the length it pads. */
 int avc_plan_create(const avc_model_cfg* cfg, int B, int T, int T_cond, avc_plan** out);
 /* flags: AVC_PLAN_INFERENCE = forward only (AE.inference, model.py:387-391): no gradient / slab / dy buffers in
- * the workspace, avc_loss / avc_backward are refused; AVC_PLAN_SPEAKER_ONLY (implies INFERENCE) = only the
- * speaker encoder runs (AE.get_speaker_embeddings, model.py:393-395): T is ignored, the result is ws["emb"]. */
+ * the workspace, avc_loss / avc_backward are refused; AVC_PLAN_SPEAKER_ONLY (implies INFERENCE unless AVC_PLAN_PART_GRADS is set) = only
+ * the speaker encoder runs (AE.get_speaker_embeddings, model.py:393-395): T is ignored, the result is ws["emb"]. */
 #define AVC_PLAN_INFERENCE 1
 #define AVC_PLAN_SPEAKER_ONLY 2
+/* PART PLANS: one of the three networks alone, the reference's sub-module calls (AE.forward / AE.inference are a few lines that call
+ * them, model.py:380-395).  At most one part flag; each combines with AVC_PLAN_X3 / AVC_PLAN_BF16S / avc_plan_set_compute_dtype as a
+ * whole plan does, and a branch runs the SAME kernel instances in a part plan as in a whole plan of that (B, T) (the launch choice is a
+ * function of the layer and its shape only).  A part plan packs only its branch's weight images and allocates only its branch's buffers
+ * (avc_plan_workspace_floats is smaller than a whole plan's); it still takes the full flat parameter buffer (same avc_plan_param_info)
+ * and a backward writes exactly its branch's avc_plan_param_range (AVC_GRADS_SPEAKER / _CONTENT / _DECODER) of `grads`, nothing else.
+ * Without AVC_PLAN_PART_GRADS a part plan is forward-only (implies AVC_PLAN_INFERENCE: no gradient buffers, backward refused);
+ * avc_loss is refused on every part plan.  Nothing here allocates or synchronises beyond what avc_plan_create* does for any plan.
+ *  - AVC_PLAN_SPEAKER_ONLY (SpeakerEncoder.forward, model.py:265-277): avc_forward(_ex) -> ws["emb"] [B, c_cond]; T is ignored.
+ *    With PART_GRADS: avc_backward with d_emb_up only (d_dec, d_muls_up NULL).
+ *  - AVC_PLAN_CONTENT_ONLY (ContentEncoder.forward, model.py:301-323): avc_forward(_ex) with x_cond and eps ignored -> ws["muls"]
+ *    [B, 2 c_out, Tb] (mu | log_sigma).  With PART_GRADS: avc_backward with d_muls_up (d_dec, d_emb_up NULL); lambda_kl adds the KL
+ *    term of solver.py:86-88 as for a whole plan.
+ *  - AVC_PLAN_DECODER_ONLY (Decoder.forward, model.py:347-371): create with T = Tb, the latent length the caller supplies (T_cond is
+ *    ignored; Tb must satisfy the decoder's reflect-pad rule); avc_plan_out_len = Tb * prod(upsample).  It runs through
+ *    avc_decoder_forward / avc_decoder_backward below, never avc_forward / avc_backward. */
+#define AVC_PLAN_CONTENT_ONLY 32
+#define AVC_PLAN_DECODER_ONLY 64
+#define AVC_PLAN_PART_GRADS 128
 int avc_plan_create_ex(const avc_model_cfg* cfg, int B, int T, int T_cond, int flags, avc_plan** out);
 int avc_plan_flags(const avc_plan* p);
 /* priority class of the device's shared side stream this plan runs its side branch on: 1 = highest, 0 = normal, -1 = the plan has no
@@ -253,6 +272,19 @@ int avc_loss(const avc_plan* p, const float* x, long sxb, long sxc, int sxt, flo
 int avc_backward(const avc_plan* p, const float* params, const float* x, long sxb, long sxc, int sxt,
                  const float* x_cond, long scb, long scc, int sct, const float* eps, const float* d_dec,
                  const float* d_muls_up, const float* d_emb_up, float lambda_kl, float* grads, float* ws, void* stream);
+
+/* ---- decoder part plans (AVC_PLAN_DECODER_ONLY): Decoder.forward(z, cond) (model.py:347-371) and its autograd.
+ * z: [B, c_in, Tb] with any element strides (szb, szc, szt); emb: [B, c_cond] with any strides (seb, sec).  Both are read in
+ * place (fp32 plans: the in_conv and its weight gradient read z, the AdaIN affine GEMM and its weight gradient read emb; AVC_PLAN_BF16S
+ * plans first convert z to bf16 pairs).  Enqueue only: no allocation, no synchronisation, graph-capture safe.
+ * avc_decoder_forward leaves ws["dec"] [B, M, Tb * prod(upsample)]; flags: AVC_FWD_WEIGHTS_PACKED as for avc_forward_ex.
+ * avc_decoder_backward (AVC_PLAN_PART_GRADS plans, after avc_decoder_forward with the same z / emb / params): d_dec [B, M, Tout]
+ * contiguous (NULL = ws["d_dec"]); writes the decoder's range of `grads` and leaves ws["d_z"] ([B, c_in, Tb] fp32 contiguous) and
+ * ws["d_emb"] ([B, c_cond] fp32 row-major): the gradients with respect to the caller's z and emb (no reparameterisation step runs). */
+int avc_decoder_forward(const avc_plan* p, const float* params, const float* z, long szb, long szc, int szt, const float* emb, long seb,
+                        long sec, float* ws, int flags, void* stream);
+int avc_decoder_backward(const avc_plan* p, const float* params, const float* z, long szb, long szc, int szt, const float* emb, long seb,
+                         long sec, const float* d_dec, float* grads, float* ws, void* stream);
 
 /* ---- bf16 PAIR storage (compute_dtype "bf16", BASELINE configs[2]): an activation tensor [B, C, T] is a DWORD tensor [B][C/2][T],
  * dword (b, p, t) = bf16(channel 2p) in the low half, bf16(channel 2p + 1) in the high half; statistics and accumulation stay fp32.
