@@ -46,6 +46,7 @@ PLAN_X3 = 4
 PLAN_RAGGED = 8
 PLAN_BF16S = 16
 PLAN_CONTENT_ONLY, PLAN_DECODER_ONLY, PLAN_PART_GRADS = 32, 64, 128   # part plans (one network; PART_GRADS: with its backward)
+PLAN_INPUT_GRADS = 256   # avc_backward also leaves d(loss)/d(x) in ws["d_x"] (and ws["d_x_cond"])
 FWD_WEIGHTS_PACKED = 1   # avc_forward_ex: the caller packed the weight images behind its optimizer step (avc_plan_pack_weights)
 ERR_PAIR_SHAPE = -12   # avc_plan_create*: the shape is outside the bf16 pair kernels (odd channel count / frames not a multiple of 4)
 c_void_p, c_long, c_int, c_float = ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_float

@@ -116,5 +116,6 @@ int avc_launch_dense(const DenseArgs& a, int backward, hipStream_t s);
 int avc_launch_gather_segments(const float* corpus, long n_rows, int M, const long* starts, int B, int T, float* out,
                                hipStream_t s);
 int avc_launch_add_transposed(float* dst, const float* src, int B, int C, hipStream_t s);
+int avc_launch_add(float* dst, const float* src, long n, hipStream_t s);   // dst[i] += src[i]
 int avc_launch_transpose(float* dst, const float* src, int R, int C, hipStream_t s);   // dst[c][r] = src[r][c]
 

@@ -60,6 +60,7 @@ struct LayerP {
     bool conv_path = true;             // launched through conv_gemm.hip (AVC_IMG_K4 images); false: the dense stack (AVC_IMG_PLAIN)
     long wplain = -1;                  // extra AVC_IMG_PLAIN forward image (the affine layer: its d_emb GEMM reads it as a [Kp][Mp] matrix)
     bool bh = false;                   // bf16 pair operands (AVC_PLAN_BF16S): AVC_IMG_K4H images over Cin / 2 (Cout / 2) dword channels
+    long src_off = 0;                  // input-gradient image of input rows [src_off, src_off + dgM) of w[0] only (the in_conv's pass-through rows)
 };
 
 struct EncNet {
@@ -69,6 +70,8 @@ struct EncNet {
     int T[AVC_MAX_BLOCKS + 1];
     std::vector<int> bank, c1, c2, dn1, dn2;
     int in_conv = -1, outl = -1, heads = -1;
+    int in_pass = -1;                               // AVC_PLAN_INPUT_GRADS: input-gradient image of the in_conv's M pass-through rows
+    long dx = -1;                                   // AVC_PLAN_INPUT_GRADS: d(loss)/d(x) [B, M, T0] fp32
     long cat = -1, dcat = -1, h0 = -1;              // h0: speaker relu(in_conv) / content y0
     long out[AVC_MAX_BLOCKS + 1];                   // block outputs (out[0] = after in_conv stage)
     long a1[AVC_MAX_BLOCKS], a2[AVC_MAX_BLOCKS];    // speaker: relu outputs; content: a1 = relu(IN(y1))
@@ -280,7 +283,7 @@ extern "C" int avc_plan_create_ex(const avc_model_cfg* cfg, int B, int T, int T_
 
 extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int T_cond, int flags, const avc_tuning* tuning, avc_plan** out) {
     if (!cfg || !out || B < 1 || T < 1) return fail(-1, "avc_plan_create: bad arguments");
-    if (flags & ~(AVC_PLAN_INFERENCE | AVC_PLAN_PARTS | AVC_PLAN_PART_GRADS | AVC_PLAN_X3 | AVC_PLAN_BF16S)) return fail(-1, "avc_plan_create: unknown flag");
+    if (flags & ~(AVC_PLAN_INFERENCE | AVC_PLAN_PARTS | AVC_PLAN_PART_GRADS | AVC_PLAN_X3 | AVC_PLAN_BF16S | AVC_PLAN_INPUT_GRADS)) return fail(-1, "avc_plan_create: unknown flag");
     if ((flags & AVC_PLAN_X3) && (flags & AVC_PLAN_BF16S)) return fail(-1, "avc_plan_create: AVC_PLAN_X3 and AVC_PLAN_BF16S exclude each other");
     if (tuning && tuning->struct_size != (int)sizeof(avc_tuning)) return fail(-1, "avc_plan_create_tuned: avc_tuning of another library version (use avc_tuning_init)");
     const int part = flags & AVC_PLAN_PARTS;
@@ -288,8 +291,11 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
     if ((flags & AVC_PLAN_PART_GRADS) && !part) return fail(-1, "avc_plan_create: AVC_PLAN_PART_GRADS needs a part flag (whole plans have gradient buffers unless AVC_PLAN_INFERENCE)");
     if ((flags & AVC_PLAN_PART_GRADS) && (flags & AVC_PLAN_INFERENCE)) return fail(-1, "avc_plan_create: AVC_PLAN_PART_GRADS and AVC_PLAN_INFERENCE exclude each other");
     if (part && !(flags & AVC_PLAN_PART_GRADS)) flags |= AVC_PLAN_INFERENCE;   // a part plan is forward-only unless asked for its gradients
+    if ((flags & AVC_PLAN_INPUT_GRADS) && (flags & (AVC_PLAN_INFERENCE | AVC_PLAN_DECODER_ONLY)))
+        return fail(-1, "avc_plan_create: AVC_PLAN_INPUT_GRADS needs a plan with a backward pass through an encoder (not INFERENCE, not DECODER_ONLY, part plans need PART_GRADS)");
     if (T_cond <= 0) T_cond = T;
     const bool infer = (flags & AVC_PLAN_INFERENCE) != 0;
+    const bool ig = (flags & AVC_PLAN_INPUT_GRADS) != 0;
     const bool dec_only = (flags & AVC_PLAN_DECODER_ONLY) != 0;
     const bool do_spk = has_spk(flags), do_enc = has_enc(flags), do_dec = has_dec(flags);
     if (validate_enc(cfg->spk, true) || validate_enc(cfg->enc, false)) return fail(-2, "avc_plan_create: unsupported encoder config");
@@ -402,8 +408,23 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
     const bool dg = !infer;
     for (EncNet* e : {&p->spk, &p->enc}) {
         if (!(e == &p->enc ? do_enc : do_spk)) continue;
-        for (int id : e->bank) finish_layer(p, p->layers[id], false, 0, B, e->T[0], e->T[0], e->nb);
+        for (int id : e->bank) finish_layer(p, p->layers[id], ig, 0, B, e->T[0], e->T[0], e->nb);
         finish_layer(p, p->layers[e->in_conv], dg, e->CC - e->c.c_in, B, e->T[0], e->T[0]);
+        if (ig) {   // the in_conv's input gradient for its last M input rows (x itself, model.py:90): w[0] rows [nb c_bank, CC)
+            LayerP L = p->layers[e->in_conv];
+            L.src_off = (long)e->nb * e->c.c_bank;
+            L.x3_f = L.x3_d = false;
+            L.wpf = L.wrs_f = L.wrs_d = L.wplain = L.bpk = -1;
+            L.need_dgrad = true;
+            L.dgM = e->c.c_in;
+            L.Mp_d = avc_cdiv(L.dgM, 128) * 128;
+            const int td = avc_conv_pick_tile(p->tun, L.Mp_d, B, e->T[0], 1, L.Cout * L.KS);
+            L.CKd = avc_conv_ck_for(p->tun, L.KS, avc_conv_num_wgs(td, L.Mp_d, B, e->T[0], 1), 1, L.stride, e->T[0], td);
+            L.nchunk_d = avc_cdiv(L.bh ? L.Cout / 2 : L.Cout, L.CKd);
+            L.wpd = p->alloc((long)L.nchunk_d * L.KS * L.CKd * L.Mp_d);
+            p->layers.push_back(L);
+            e->in_pass = (int)p->layers.size() - 1;
+        }
         for (int l = 0; l < e->n; ++l) {
             finish_layer(p, p->layers[e->c1[l]], dg, 0, B, e->T[l], e->T[l]);
             finish_layer(p, p->layers[e->c2[l]], dg, 0, B, e->T[l + 1], e->T[l]);
@@ -437,6 +458,7 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
         const long C = e.c.c_h / H;
         e.cat = p->alloc(Bl * (e.CC / H) * e.T[0]);
         if (!infer) e.dcat = p->alloc(Bl * (e.CC / H) * e.T[0]);
+        if (ig) e.dx = p->alloc(Bl * e.c.c_in * e.T[0]);
         e.h0 = p->alloc(Bl * C * e.T[0]);
         e.out[0] = spk ? e.h0 : p->alloc(Bl * C * e.T[0]);
         if (!spk) e.st0 = p->alloc(2 * Bl * e.c.c_h);
@@ -555,6 +577,10 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
             p->named["d_z"] = p->dz;
             p->named["d_emb"] = dec_only ? p->demb_rm : p->demb;
             p->named["d_cond"] = d.dcond;
+        }
+        if (ig) {
+            p->named["d_x"] = do_enc ? p->enc.dx : p->spk.dx;
+            if (do_enc && do_spk) p->named["d_x_cond"] = p->spk.dx;
         }
     }
 
@@ -687,7 +713,7 @@ static void plan_init_pack_table(avc_plan* p) {
     std::vector<PackArgs> all;
     for (int pass = 0; pass < 2; ++pass) {
         for (size_t i = 0; i < p->layers.size(); ++i)
-            if (p->layers[i].wpf >= 0 && (early[i] != 0) == (pass == 0)) pack_layer(p, p->layers[i], (const float*)nullptr, (float*)nullptr, all);
+            if ((p->layers[i].wpf >= 0 || p->layers[i].wpd >= 0) && (early[i] != 0) == (pass == 0)) pack_layer(p, p->layers[i], (const float*)nullptr, (float*)nullptr, all);
         if (pass == 0) p->pack_early_imgs = (int)all.size();
     }
     if (all.empty()) return;
@@ -1044,12 +1070,15 @@ static void pack_layer(const avc_plan* p, const LayerP& L, const float* params, 
     PackArgs a;
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < L.nsrc; ++i) a.src[i] = p->par(params, L.w[i]);
+    a.src[0] += L.src_off;   // (rows [src_off, src_off + dgM) of a forward input: the pack's input-gradient index stays below Cout Cin KS)
     a.nsrc = L.nsrc; a.rows_per_src = L.rows;
     a.Cout = L.Cout; a.Cin = L.Cin; a.KS = L.KS;
     a.dgrad = 0; a.CK = L.CK; a.nchunk = L.nchunk_f; a.M = L.Cout; a.Mp = L.Mp_f;
     a.dst = ws + L.wpf;
     a.img = L.conv_path ? (L.bh ? AVC_IMG_K4H : AVC_IMG_K4) : AVC_IMG_PLAIN;
-    if (L.x3_f) {   // only the image the launch will read
+    if (L.wpf < 0) {
+        // (an input-gradient image only: EncNet::in_pass)
+    } else if (L.x3_f) {   // only the image the launch will read
         PackArgs r;
         avc_pack_x3_args(r, p->par(params, L.w[0]), L.Cout, L.Cin, L.KS, 0, ws + L.wrs_f);
         out.push_back(r);
@@ -1180,7 +1209,7 @@ static int pack_all(const avc_plan* p, const float* params, float* ws, hipStream
     }
     std::vector<PackArgs> all;
     for (size_t i = 0; i < p->layers.size(); ++i)
-        if (p->layers[i].wpf >= 0) pack_layer(p, p->layers[i], params, ws, all);
+        if (p->layers[i].wpf >= 0 || p->layers[i].wpd >= 0) pack_layer(p, p->layers[i], params, ws, all);
     return avc_launch_pack_batch(all.data(), (int)all.size(), s);
 }
 
@@ -1444,6 +1473,22 @@ static int enc_back_front(BwdCtx& c, const EncNet& e, const float* x, long sxb, 
         a.g[0].out2 = ws + e.dcat;
         a.g[0].mask = ws + e.cat;
         RUN(avc_launch_conv(a, c.s, 0, p->tun));
+    }
+    if (!c.dry && e.in_pass >= 0) {
+        // AVC_PLAN_INPUT_GRADS: d(x) = W_in[:, nb c_bank:]^T dy_in + sum_g bank_g^T(dcat_g), one implicit-GEMM input-gradient launch per
+        // term, each adding the previous partial sum (the residual join of its epilogue, in place) -- a fixed order, no atomics.  The
+        // reflect-pad adjoint of every bank width is folded into the launch's fetch (mirror windows).  fp32 output in every mode.
+        const long M = e.c.c_in;
+        float* dx = ws + e.dx;
+        ConvArgs a = mk_dgrad(SL, p->layers[e.in_pass], ws, dy_in, (long)C * T0, T0, 1, 1, B, T0, T0, dx, M * T0, T0, 1);
+        a.pairs = 0;
+        RUN(avc_launch_conv(a, c.s, 0, p->tun));
+        for (int g = 0; g < e.nb; ++g) {
+            ConvArgs b = mk_dgrad(SL, p->layers[e.bank[g]], ws, ws + e.dcat + (long)g * Cbr * T0, CCr * T0, T0, 1, 1, B, T0, T0, dx, M * T0, T0, 1);
+            b.pairs = 0;
+            set_res(b, dx, AVC_RES_IDENTITY, M * T0, T0, 1, T0);
+            RUN(avc_launch_conv(b, c.s, 0, p->tun));
+        }
     }
     for (int g = 0; g < e.nb; ++g) {
         const LayerP& Lb = p->layers[e.bank[g]];
@@ -1912,11 +1957,17 @@ extern "C" int avc_backward(const avc_plan* p, const float* params, const float*
         return fail(-1, "avc_backward: a content part plan takes d_muls_up only (d_dec and d_emb_up must be NULL)");
     if ((p->flags & AVC_PLAN_SPEAKER_ONLY) && (d_dec || d_muls_up || !d_emb_up))
         return fail(-1, "avc_backward: a speaker part plan takes d_emb_up only (d_dec and d_muls_up must be NULL)");
+    const bool one_input = !x_cond;   // AE.forward: both encoders read x (a separate x_cond is another input, whatever memory it shares)
     if (!x_cond) {
         x_cond = x; scb = sxb; scc = sxc; sct = sxt;
     }
-    return avc_backward_impl(p, params, x, sxb, sxc, sxt, x_cond, scb, scc, sct, eps, d_dec, d_muls_up, d_emb_up, lambda_kl,
-                             grads, ws, (hipStream_t)stream, false, nullptr);
+    const int rc = avc_backward_impl(p, params, x, sxb, sxc, sxt, x_cond, scb, scc, sct, eps, d_dec, d_muls_up, d_emb_up, lambda_kl,
+                                     grads, ws, (hipStream_t)stream, false, nullptr);
+    if (rc) return rc;
+    // d(x) of a single input: the speaker encoder's term onto the content encoder's, behind the join of the two branches (fixed order)
+    if (one_input && (p->flags & AVC_PLAN_INPUT_GRADS) && has_spk(p->flags) && has_enc(p->flags) && p->spk.T[0] == p->enc.T[0])
+        RUN(avc_launch_add(ws + p->enc.dx, ws + p->spk.dx, (long)p->B * p->M * p->T, (hipStream_t)stream));
+    return 0;
 }
 
 // autograd of Decoder.forward (model.py:347-371) on a decoder part plan with AVC_PLAN_PART_GRADS: the decoder's parameter gradients,

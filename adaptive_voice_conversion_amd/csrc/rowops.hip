@@ -357,6 +357,11 @@ __global__ void __launch_bounds__(AVC_THREADS) add_transposed_kernel(float* dst,
     dst[e] += src[(long)b * C + c];
 }
 
+// dst[i] += src[i] (AVC_PLAN_INPUT_GRADS: the speaker encoder's d(x) onto the content encoder's when both read the same x)
+__global__ void __launch_bounds__(AVC_THREADS) add_kernel(float* dst, const float* src, long n) {
+    for (long e = (long)blockIdx.x * AVC_THREADS + threadIdx.x; e < n; e += (long)gridDim.x * AVC_THREADS) dst[e] += src[e];
+}
+
 // dst[c][r] = src[r][c]: an [R][C] matrix to [C][R] (part plans: d(emb) between the caller's row-major [B, c_cond] and the channel-major
 // layout of the dense stack / the affine GEMM)
 __global__ void __launch_bounds__(AVC_THREADS) transpose_kernel(float* dst, const float* src, int R, int C) {
@@ -667,6 +672,12 @@ int avc_launch_gather_segments(const float* corpus, long n_rows, int M, const lo
 int avc_launch_add_transposed(float* dst, const float* src, int B, int C, hipStream_t s) {
     ProfScope ps(AVC_K_MISC, 0.0, 0.0, s);
     hipLaunchKernelGGL(add_transposed_kernel, dim3(avc_cdiv(B * C, AVC_THREADS)), dim3(AVC_THREADS), 0, s, dst, src, B, C);
+    return (int)hipGetLastError();
+}
+int avc_launch_add(float* dst, const float* src, long n, hipStream_t s) {
+    if (n < 1) return -1;
+    ProfScope ps(AVC_K_MISC, 0.0, 12.0 * (double)n, s);
+    hipLaunchKernelGGL(add_kernel, dim3(ew_blocks(n)), dim3(AVC_THREADS), 0, s, dst, src, n);
     return (int)hipGetLastError();
 }
 int avc_launch_transpose(float* dst, const float* src, int R, int C, hipStream_t s) {

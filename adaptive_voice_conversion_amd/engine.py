@@ -102,7 +102,10 @@ class Plan:
     MODES = {"train": 0, "inference": _lib.PLAN_INFERENCE, "speaker": _lib.PLAN_INFERENCE | _lib.PLAN_SPEAKER_ONLY,
              "content": _lib.PLAN_INFERENCE | _lib.PLAN_CONTENT_ONLY, "decoder": _lib.PLAN_INFERENCE | _lib.PLAN_DECODER_ONLY,
              "speaker_train": _lib.PLAN_SPEAKER_ONLY | _lib.PLAN_PART_GRADS, "content_train": _lib.PLAN_CONTENT_ONLY | _lib.PLAN_PART_GRADS,
-             "decoder_train": _lib.PLAN_DECODER_ONLY | _lib.PLAN_PART_GRADS}
+             "decoder_train": _lib.PLAN_DECODER_ONLY | _lib.PLAN_PART_GRADS,
+             # ... whose backward also leaves d(loss)/d(x) in ws["d_x"] (and d(loss)/d(x_cond) in ws["d_x_cond"])
+             "ig_train": _lib.PLAN_INPUT_GRADS, "speaker_ig_train": _lib.PLAN_SPEAKER_ONLY | _lib.PLAN_PART_GRADS | _lib.PLAN_INPUT_GRADS,
+             "content_ig_train": _lib.PLAN_CONTENT_ONLY | _lib.PLAN_PART_GRADS | _lib.PLAN_INPUT_GRADS}
     COMPUTE = {"fp32": 0, "float32": 0, "f32": 0, "fp32x3": 0, "f32x3": 0, "bf16": 3, "bfloat16": 3, "bf16s": 3, "bf16_storage": 3,
                "bf16r": 1, "bf16_operands": 1}
 
@@ -118,7 +121,8 @@ class Plan:
         mode: "train" (forward + loss + backward), "inference" (forward only: the workspace holds no gradient,
         slab or dy buffers) or "speaker" (only the speaker encoder runs, AE.get_speaker_embeddings); part plans of ONE network
         (SpeakerEncoder / ContentEncoder / Decoder.forward, model.py:265-277 / 301-323 / 347-371): "speaker", "content" and "decoder"
-        run forward only, "speaker_train", "content_train" and "decoder_train" also their backward.  A decoder plan takes
+        run forward only, "speaker_train", "content_train" and "decoder_train" also their backward; "ig_train", "speaker_ig_train" and
+        "content_ig_train" are "train" / "speaker_train" / "content_train" whose backward also computes the input gradients.  A decoder plan takes
         T = the latent length Tb of its input z and runs through ``decoder_forward`` / ``decoder_backward``.
         device: the plan's helper streams are created on it (default: the current device).
         tuning: {avc_tuning field: value} overrides of the launch heuristics / diagnostic switches the plan captures
@@ -277,10 +281,11 @@ class Plan:
             self._chk(self.lib.avc_loss(self.h, _ptr(x), x.stride(0), x.stride(1), x.stride(2), float(lambda_rec), _ptr(ws), _stream(ws)))
 
     def backward(self, params, x, x_cond, eps, grads, ws, d_dec=None, d_muls=None, d_emb=None, lambda_kl=0.0):
-        xc = x if x_cond is None else x_cond
+        """x_cond None: both encoders read x (AE.forward; with AVC_PLAN_INPUT_GRADS ws["d_x"] then holds both encoders' terms)."""
+        sc = (0, 0, 0) if x_cond is None else x_cond.stride()
         with _on(ws):
-            self._chk(self.lib.avc_backward(self.h, _ptr(params), _ptr(x), x.stride(0), x.stride(1), x.stride(2), _ptr(xc),
-                                            xc.stride(0), xc.stride(1), xc.stride(2), _ptr(eps), _ptr(d_dec), _ptr(d_muls),
+            self._chk(self.lib.avc_backward(self.h, _ptr(params), _ptr(x), x.stride(0), x.stride(1), x.stride(2), _ptr(x_cond),
+                                            sc[0], sc[1], sc[2], _ptr(eps), _ptr(d_dec), _ptr(d_muls),
                                             _ptr(d_emb), float(lambda_kl), _ptr(grads), _ptr(ws), _stream(ws)))
 
 

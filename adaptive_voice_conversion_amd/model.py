@@ -182,11 +182,13 @@ class _AEFunction(torch.autograd.Function):
     it ran in as pending until its backward() has consumed it; a second autograd forward of the same shape
     that arrives meanwhile (micro-batches, an extra evaluation pass with grad enabled) gets a private
     workspace instead of overwriting the saved activations.  no_grad / inference / embedding calls run in
-    separate forward-only plans and never touch a training workspace."""
+    separate forward-only plans and never touch a training workspace.  When x requires grad the pass runs in a plan whose backward
+    also computes x.grad (AVC_PLAN_INPUT_GRADS: both encoders' terms)."""
 
     @staticmethod
     def forward(ctx, ae, x, eps, *params):
-        entry = ae._entry("train", x.shape[0], x.shape[2], x.shape[2], x.device)
+        mode = "ig_train" if ctx.needs_input_grad[1] else "train"
+        entry = ae._entry(mode, x.shape[0], x.shape[2], x.shape[2], x.device)
         plan, ws = entry.plan, entry.ws
         if entry.busy():
             ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=x.device)   # private to this forward
@@ -221,8 +223,44 @@ class _AEFunction(torch.autograd.Function):
         g = torch.empty_like(ae._flat)
         plan.backward(ae._flat, x, None, eps, g, ws, d_dec=d_dec, d_muls=d_muls, d_emb=d_emb, lambda_kl=0.0)
         ctx.token.done = True
+        dx = plan.view(ws, "d_x", tuple(x.shape)).clone() if ctx.needs_input_grad[1] else None
         grads = tuple(g[off:off + n].view(shape) for off, n, shape in ae._layout)
-        return (None, None, None) + grads
+        return (None, dx, None) + grads
+
+
+class _InferenceFunction(torch.autograd.Function):
+    """AE.inference(x, x_cond) (model.py:387-391) with autograd, for inputs that require grad (adversarial perturbations of the target
+    utterance, saliency maps): a whole plan with AVC_PLAN_INPUT_GRADS, no reparameterisation (eps = None: z = mu).  Returns d(x),
+    d(x_cond) and the parameters' gradients.  x_cond may be x itself: the engine then sums both encoders' terms into d(x)."""
+
+    @staticmethod
+    def forward(ctx, ae, x, x_cond, *params):
+        B, T, Tc = x.shape[0], x.shape[2], x_cond.shape[2]
+        entry = ae._entry("ig_train", B, T, Tc, x.device)
+        plan, ws = entry.plan, entry.ws
+        if entry.busy():
+            ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=x.device)   # private to this forward
+        token = _Token()
+        if ws is entry.ws:
+            entry.pending = weakref.ref(token)
+        same = x_cond is x   # one autograd input read by both encoders (x.detach() or another view of its memory is a separate input)
+        plan.forward(ae._flat, x, None if same else x_cond, None, ws)
+        ctx.ae, ctx.plan, ctx.ws, ctx.token, ctx.same = ae, plan, ws, token, same
+        ctx.save_for_backward(x, x_cond)
+        return ae._outputs(plan, ws)[2].clone()
+
+    @staticmethod
+    def backward(ctx, d_dec):
+        _PartFunction._check(ctx)
+        x, x_cond = ctx.saved_tensors
+        ae, plan, ws = ctx.ae, ctx.plan, ctx.ws
+        g = torch.empty_like(ae._flat)
+        plan.backward(ae._flat, x, None if ctx.same else x_cond, None, g, ws, d_dec=d_dec.contiguous().float(), lambda_kl=0.0)
+        ctx.token.done = True
+        dx = plan.view(ws, "d_x", tuple(x.shape)).clone() if (ctx.needs_input_grad[1] or ctx.same) else None
+        dxc = None if ctx.same else (plan.view(ws, "d_x_cond", tuple(x_cond.shape)).clone() if ctx.needs_input_grad[2] else None)
+        grads = tuple(g[off:off + n].view(shape) for off, n, shape in ae._layout)
+        return (None, dx, dxc) + grads
 
 
 class _PartFunction(torch.autograd.Function):
@@ -257,12 +295,13 @@ class _PartFunction(torch.autograd.Function):
 
 
 class _SpeakerFunction(_PartFunction):
-    """SpeakerEncoder.forward (model.py:265-277) with autograd: x gets no gradient, as in AE.forward."""
+    """SpeakerEncoder.forward (model.py:265-277) with autograd; x gets its gradient when it requires one (a plan with
+    AVC_PLAN_INPUT_GRADS)."""
 
     @staticmethod
     def forward(ctx, ae, x, *params):
         B, T = x.shape[0], x.shape[2]
-        plan, ws = _PartFunction._begin(ctx, ae, "speaker_train", B, T, x.device)
+        plan, ws = _PartFunction._begin(ctx, ae, "speaker_ig_train" if ctx.needs_input_grad[1] else "speaker_train", B, T, x.device)
         plan.forward(ae._flat, x, None, None, ws)
         ctx.save_for_backward(x)
         return plan.view(ws, "emb", (B, ae._c_emb)).clone()
@@ -273,16 +312,18 @@ class _SpeakerFunction(_PartFunction):
         x, = ctx.saved_tensors
         g = torch.empty_like(ctx.ae._flat)
         ctx.plan.backward(ctx.ae._flat, x, None, None, g, ctx.ws, d_emb=d_emb.contiguous().float())
-        return (None, None) + _PartFunction._grads(ctx, g, "speaker")
+        dx = ctx.plan.view(ctx.ws, "d_x", tuple(x.shape)).clone() if ctx.needs_input_grad[1] else None
+        return (None, dx) + _PartFunction._grads(ctx, g, "speaker")
 
 
 class _ContentFunction(_PartFunction):
-    """ContentEncoder.forward (model.py:301-323) with autograd: x gets no gradient, as in AE.forward."""
+    """ContentEncoder.forward (model.py:301-323) with autograd; x gets its gradient when it requires one (a plan with
+    AVC_PLAN_INPUT_GRADS)."""
 
     @staticmethod
     def forward(ctx, ae, x, *params):
         B, T = x.shape[0], x.shape[2]
-        plan, ws = _PartFunction._begin(ctx, ae, "content_train", B, T, x.device)
+        plan, ws = _PartFunction._begin(ctx, ae, "content_ig_train" if ctx.needs_input_grad[1] else "content_train", B, T, x.device)
         plan.forward(ae._flat, x, None, None, ws)
         ctx.save_for_backward(x)
         muls = plan.view(ws, "muls", (B, 2 * ae._c_lat, plan.latent_len))
@@ -301,7 +342,8 @@ class _ContentFunction(_PartFunction):
             d_muls[:, C:] = d_ls
         g = torch.empty_like(ae._flat)
         plan.backward(ae._flat, x, None, None, g, ctx.ws, d_muls=d_muls, lambda_kl=0.0)
-        return (None, None) + _PartFunction._grads(ctx, g, "content")
+        dx = plan.view(ctx.ws, "d_x", tuple(x.shape)).clone() if ctx.needs_input_grad[1] else None
+        return (None, dx) + _PartFunction._grads(ctx, g, "content")
 
 
 class _DecoderFunction(_PartFunction):
@@ -368,7 +410,9 @@ class AE(nn.Module):
         # train: the regular batch + the short last batch of an epoch; inference / speaker: a few recent shapes
         self._plans = _PlanCache({"train": 2, "inference": 8, "speaker": 4,
                                   # sub-module calls (part plans): forward-only / with backward
-                                  "content": 4, "decoder": 4, "speaker_train": 2, "content_train": 2, "decoder_train": 2})
+                                  "content": 4, "decoder": 4, "speaker_train": 2, "content_train": 2, "decoder_train": 2,
+                                  # ... and the plans whose backward also computes the inputs' gradients (inputs that require grad)
+                                  "ig_train": 2, "speaker_ig_train": 2, "content_ig_train": 2})
         self._ragged = {}   # (lengths, device) -> (RaggedPlan, None), a few most recent
         self._ragged_ws = None   # the one workspace they share
         self.last_ragged_compute = None
@@ -476,8 +520,8 @@ class AE(nn.Module):
         x = self._prep(x)
         self._check_device(x)
         B, T = x.shape[0], x.shape[2]
-        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        mode = "train" if grad else "inference"
+        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        mode = ("ig_train" if x.requires_grad else "train") if grad else "inference"   # (the plan _AEFunction runs in)
         if eps is None:
             Tb = self._plan(B, T, T, x.device, mode)[0].latent_len
             eps = torch.randn(B, self._c_lat, Tb, device=x.device, dtype=torch.float32)
@@ -494,6 +538,9 @@ class AE(nn.Module):
         """model.py:387-391: decoder(mu(x), speaker(x_cond)); lengths may differ."""
         x, x_cond = self._prep(x), self._prep(x_cond)
         self._check_device(x)
+        if torch.is_grad_enabled() and (x.requires_grad or x_cond.requires_grad):
+            self._check_device(x_cond)
+            return _InferenceFunction.apply(self, x, x_cond, *self.parameters())
         plan, ws = self._plan(x.shape[0], x.shape[2], x_cond.shape[2], x.device, "inference")
         plan.forward(self._flat, x, x_cond, None, ws)
         return self._outputs(plan, ws)[2].clone()
@@ -541,8 +588,8 @@ class AE(nn.Module):
     def _speaker_forward(self, x):
         x = self._prep(x)
         self._check_device(x)
-        if self._part_grad("speaker"):
-            return _SpeakerFunction.apply(self, x.detach(), *self.speaker_encoder.parameters())
+        if self._part_grad("speaker", x):
+            return _SpeakerFunction.apply(self, x, *self.speaker_encoder.parameters())
         plan, ws = self._plan(x.shape[0], x.shape[2], x.shape[2], x.device, "speaker")
         plan.forward(self._flat, x, None, None, ws)
         return plan.view(ws, "emb", (x.shape[0], self._c_emb)).clone()
@@ -550,8 +597,8 @@ class AE(nn.Module):
     def _content_forward(self, x):
         x = self._prep(x)
         self._check_device(x)
-        if self._part_grad("content"):
-            return _ContentFunction.apply(self, x.detach(), *self.content_encoder.parameters())
+        if self._part_grad("content", x):
+            return _ContentFunction.apply(self, x, *self.content_encoder.parameters())
         plan, ws = self._plan(x.shape[0], x.shape[2], x.shape[2], x.device, "content")
         plan.forward(self._flat, x, None, None, ws)
         muls = plan.view(ws, "muls", (x.shape[0], 2 * self._c_lat, plan.latent_len))
@@ -570,9 +617,12 @@ class AE(nn.Module):
         return plan.view(ws, "dec", (z.shape[0], self._n_mels, plan.out_len)).clone()
 
     def get_speaker_embeddings(self, x):
-        """model.py:393-395: only the speaker encoder runs (a speaker-only plan)."""
+        """model.py:393-395: only the speaker encoder runs (a speaker-only plan).  An x that requires grad takes the autograd path of
+        ``speaker_encoder(x)``."""
         x = self._prep(x)
         self._check_device(x)
+        if torch.is_grad_enabled() and x.requires_grad:
+            return self._speaker_forward(x)
         plan, ws = self._plan(x.shape[0], x.shape[2], x.shape[2], x.device, "speaker")
         plan.forward(self._flat, x, x, None, ws)
         return plan.view(ws, "emb", (x.shape[0], self._c_emb)).clone()

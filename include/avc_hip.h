@@ -111,6 +111,18 @@ int avc_plan_create(const avc_model_cfg* cfg, int B, int T, int T_cond, avc_plan
 #define AVC_PLAN_CONTENT_ONLY 32
 #define AVC_PLAN_DECODER_ONLY 64
 #define AVC_PLAN_PART_GRADS 128
+/* AVC_PLAN_INPUT_GRADS: avc_backward also computes the gradients with respect to the input spectrograms (the reference's x.grad when
+ * x requires grad).  Combines with whole plans (not AVC_PLAN_INFERENCE) and with the speaker / content part plans that have
+ * AVC_PLAN_PART_GRADS; refused with AVC_PLAN_DECODER_ONLY.  Adds to the plan: an input-gradient weight image of every conv-bank layer
+ * (transposed, tap-flipped) and one of the in_conv's M pass-through input rows, per encoder that runs; one fp32 [B, M, T] buffer per
+ * encoder.  After avc_backward:
+ *  - ws["d_x"] [B, M, T] fp32 contiguous: d(loss)/d(x).  Whole plans called with x_cond NULL (one input read by both encoders,
+ *    AE.forward) leave there the sum of both encoders' terms: content first, then speaker, in that fixed order.  With a non-NULL
+ *    x_cond it is the content encoder's term alone -- also when x_cond points at the same memory as x.
+ *  - ws["d_x_cond"] [B, M, T_cond] fp32 contiguous (whole plans): d(loss)/d(x_cond), the speaker encoder's term, when x_cond is not
+ *    NULL (AE.inference(x, x_cond); T_cond may differ from T and eps may be NULL).
+ * Speaker part plans leave their gradient in ws["d_x"].  Plans without the flag are unchanged (weight images, workspace, launches). */
+#define AVC_PLAN_INPUT_GRADS 256
 int avc_plan_create_ex(const avc_model_cfg* cfg, int B, int T, int T_cond, int flags, avc_plan** out);
 int avc_plan_flags(const avc_plan* p);
 /* priority class of the device's shared side stream this plan runs its side branch on: 1 = highest, 0 = normal, -1 = the plan has no
