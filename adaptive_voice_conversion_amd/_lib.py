@@ -48,6 +48,7 @@ PLAN_BF16S = 16
 PLAN_CONTENT_ONLY, PLAN_DECODER_ONLY, PLAN_PART_GRADS = 32, 64, 128   # part plans (one network; PART_GRADS: with its backward)
 PLAN_INPUT_GRADS = 256   # avc_backward also leaves d(loss)/d(x) in ws["d_x"] (and ws["d_x_cond"])
 FWD_WEIGHTS_PACKED = 1   # avc_forward_ex: the caller packed the weight images behind its optimizer step (avc_plan_pack_weights)
+PLAN_EMB_INPUT = 512     # ragged plans: content encoder + decoder, the embeddings come from the caller (avc_forward_ragged_emb)
 ERR_PAIR_SHAPE = -12   # avc_plan_create*: the shape is outside the bf16 pair kernels (odd channel count / frames not a multiple of 4)
 c_void_p, c_long, c_int, c_float = ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_float
 
@@ -85,6 +86,10 @@ def declare(lib):
                                            ctypes.POINTER(c_void_p)]
     lib.avc_plan_ragged_out.argtypes = [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_long)]
     lib.avc_forward_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    if hasattr(lib, "avc_plan_create_ragged_ex"):   # (absent from older builds loaded through AVC_HIP_LIB for same-box A/B runs)
+        lib.avc_plan_create_ragged_ex.argtypes = [ctypes.POINTER(ModelCfg), c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
+                                                  ctypes.POINTER(Tuning), ctypes.POINTER(c_void_p)]
+        lib.avc_forward_ragged_emb.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]
     lib.avc_gather_segments.argtypes = [c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.avc_plan_destroy.argtypes = [c_void_p]
     lib.avc_plan_destroy.restype = None

@@ -2010,9 +2010,23 @@ static void rag_level(avc_plan* p, avc_plan::RagLevel& L, const std::vector<int>
 }
 
 extern "C" int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, const avc_tuning* tuning, avc_plan** out) {
+    return avc_plan_create_ragged_ex(cfg, B, T, T_cond, 0, tuning, out);
+}
+
+// flags: 0 = B (source, target) pairs through all three networks; AVC_PLAN_SPEAKER_ONLY = the speaker encoder over T_cond alone;
+// AVC_PLAN_EMB_INPUT = content encoder + decoder over T, the embeddings come from the caller (avc_forward_ragged_emb).  A network that
+// does not run keeps its entries of the flat parameter buffer, and gets no weight image, no level table and no buffer.
+extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, int flags, const avc_tuning* tuning,
+                                         avc_plan** out) {
+    if (flags & ~(AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_EMB_INPUT))
+        return fail(-1, "avc_plan_create_ragged_ex: unknown flag (ragged plans take AVC_PLAN_SPEAKER_ONLY or AVC_PLAN_EMB_INPUT)");
+    if ((flags & AVC_PLAN_SPEAKER_ONLY) && (flags & AVC_PLAN_EMB_INPUT))
+        return fail(-1, "avc_plan_create_ragged_ex: AVC_PLAN_SPEAKER_ONLY and AVC_PLAN_EMB_INPUT exclude each other");
+    const bool do_spk = !(flags & AVC_PLAN_EMB_INPUT), do_enc = !(flags & AVC_PLAN_SPEAKER_ONLY), do_dec = do_enc;
+    if (!do_enc) T = T_cond;   // (speaker-only: T is ignored; the shared length checks below then read T_cond twice)
     if (!cfg || !out || !T || B < 1) return fail(-1, "avc_plan_create_ragged: bad arguments");
     if (tuning && tuning->struct_size != (int)sizeof(avc_tuning)) return fail(-1, "avc_plan_create_ragged: avc_tuning of another library version (use avc_tuning_init)");
-    if (!T_cond) T_cond = T;
+    if (!T_cond || !do_spk) T_cond = T;
     if (validate_enc(cfg->spk, true) || validate_enc(cfg->enc, false)) return fail(-2, "avc_plan_create_ragged: unsupported encoder config");
     const avc_decoder_cfg& dc = cfg->dec;
     if (dc.n_conv_blocks < 1 || dc.n_conv_blocks > AVC_MAX_BLOCKS || 2 * dc.n_conv_blocks > 12 || dc.kernel_size < 1 || dc.kernel_size > 8)
@@ -2024,7 +2038,7 @@ extern "C" int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int
 
     avc_plan* p = new avc_plan();
     p->cfg = *cfg;
-    p->flags = AVC_PLAN_INFERENCE | AVC_PLAN_RAGGED;
+    p->flags = AVC_PLAN_INFERENCE | AVC_PLAN_RAGGED | flags;
     p->tun = tuning ? *tuning : avc_default_tuning();
     p->tun.ck16_wgs = -1;   // default chunk depths: the ragged launcher has the straight-line instances for those
     p->tun.ck32_wgs = -1;
@@ -2078,8 +2092,8 @@ extern "C" int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int
         }
         return 0;
     };
-    bool bad = sched(p->spk, T_cond, p->rl_spk) != 0 || sched(p->enc, T, p->rl_enc) != 0;
-    if (!bad) {
+    bool bad = (do_spk && sched(p->spk, T_cond, p->rl_spk) != 0) || (do_enc && sched(p->enc, T, p->rl_enc) != 0);
+    if (!bad && do_dec) {
         std::vector<int> cur = p->rl_enc[p->enc.n].T;
         p->rl_dec.resize(d.n + 1);
         for (int l = 0; l <= d.n && !bad; ++l) {
@@ -2100,6 +2114,7 @@ extern "C" int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int
 
     // ---- packed weights (forward images only); tile heuristics see the launch's column-tile count as its batch
     for (EncNet* e : {&p->spk, &p->enc}) {
+        if (!(e == &p->spk ? do_spk : do_enc)) continue;
         const std::vector<avc_plan::RagLevel>& lv = (e == &p->spk) ? p->rl_spk : p->rl_enc;
         for (int id : e->bank) finish_layer(p, p->layers[id], false, 0, lv[0].ntiles, 64, 64, e->nb);
         finish_layer(p, p->layers[e->in_conv], false, 0, lv[0].ntiles, 64, 64);
@@ -2108,19 +2123,23 @@ extern "C" int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int
             finish_layer(p, p->layers[e->c2[l]], false, 0, lv[l + 1].ntiles, 64, 64);
         }
     }
-    for (int l = 0; l < p->spk.nd; ++l) {
-        finish_layer(p, p->layers[p->spk.dn1[l]], false, 0, 1, B, B, 1, false);
-        finish_layer(p, p->layers[p->spk.dn2[l]], false, 0, 1, B, B, 1, false);
+    if (do_spk) {
+        for (int l = 0; l < p->spk.nd; ++l) {
+            finish_layer(p, p->layers[p->spk.dn1[l]], false, 0, 1, B, B, 1, false);
+            finish_layer(p, p->layers[p->spk.dn2[l]], false, 0, 1, B, B, 1, false);
+        }
+        finish_layer(p, p->layers[p->spk.outl], false, 0, 1, B, B, 1, false);
     }
-    finish_layer(p, p->layers[p->spk.outl], false, 0, 1, B, B, 1, false);
-    finish_layer(p, p->layers[p->enc.heads], false, 0, p->rl_dec[0].ntiles, 64, 64);
-    finish_layer(p, p->layers[d.in_conv], false, 0, p->rl_dec[0].ntiles, 64, 64);
-    for (int l = 0; l < d.n; ++l) {
-        finish_layer(p, p->layers[d.c1[l]], false, 0, p->rl_dec[l].ntiles, 64, 64);
-        finish_layer(p, p->layers[d.c2[l]], false, 0, p->rl_dec[l].ntiles, 64, 64);
+    if (do_enc) {
+        finish_layer(p, p->layers[p->enc.heads], false, 0, p->rl_dec[0].ntiles, 64, 64);
+        finish_layer(p, p->layers[d.in_conv], false, 0, p->rl_dec[0].ntiles, 64, 64);
+        for (int l = 0; l < d.n; ++l) {
+            finish_layer(p, p->layers[d.c1[l]], false, 0, p->rl_dec[l].ntiles, 64, 64);
+            finish_layer(p, p->layers[d.c2[l]], false, 0, p->rl_dec[l].ntiles, 64, 64);
+        }
+        finish_layer(p, p->layers[d.affine], false, 0, 1, B, B);
+        finish_layer(p, p->layers[d.out_conv], false, 0, p->rl_dec[d.n].ntiles, 64, 64);
     }
-    finish_layer(p, p->layers[d.affine], false, 0, 1, B, B);
-    finish_layer(p, p->layers[d.out_conv], false, 0, p->rl_dec[d.n].ntiles, 64, 64);
 
     // ---- packed activation buffers: [channels][T_b] blocks back to back
     const long Bl = B;
@@ -2151,26 +2170,30 @@ extern "C" int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int
             }
         }
     };
-    alloc_enc(p->spk, p->rl_spk, true);
     const long Cz = dc.c_in, Cd = dc.c_h;
-    p->emb = p->alloc(Bl * dc.c_cond);
-    alloc_enc(p->enc, p->rl_enc, false);
-    p->muls = p->alloc(2 * Cz * p->rl_dec[0].off[B]);
-    d.cond = p->alloc(Bl * 2 * d.n * 2 * Cd);
-    d.y0 = p->alloc(Cd * p->rl_dec[0].off[B]);
-    d.out[0] = p->alloc(Cd * p->rl_dec[0].off[B]);
-    for (int l = 0; l < d.n; ++l) {
-        d.y1[l] = p->alloc(Cd * p->rl_dec[l].off[B]);
-        d.a1[l] = p->alloc(Cd * p->rl_dec[l].off[B]);
-        d.y2[l] = p->alloc(Cd * p->rl_dec[l + 1].off[B]);
-        d.out[l + 1] = p->alloc(Cd * p->rl_dec[l + 1].off[B]);
+    if (do_spk) {
+        alloc_enc(p->spk, p->rl_spk, true);
+        p->emb = p->alloc(Bl * dc.c_cond);
+        p->named["emb"] = p->emb;
     }
-    p->decb = p->alloc((long)p->M * p->rl_dec[d.n].off[B]);
+    if (do_enc) {   // (... and the decoder: ragged plans run it whenever the content encoder runs)
+        alloc_enc(p->enc, p->rl_enc, false);
+        p->muls = p->alloc(2 * Cz * p->rl_dec[0].off[B]);
+        d.cond = p->alloc(Bl * 2 * d.n * 2 * Cd);
+        d.y0 = p->alloc(Cd * p->rl_dec[0].off[B]);
+        d.out[0] = p->alloc(Cd * p->rl_dec[0].off[B]);
+        for (int l = 0; l < d.n; ++l) {
+            d.y1[l] = p->alloc(Cd * p->rl_dec[l].off[B]);
+            d.a1[l] = p->alloc(Cd * p->rl_dec[l].off[B]);
+            d.y2[l] = p->alloc(Cd * p->rl_dec[l + 1].off[B]);
+            d.out[l + 1] = p->alloc(Cd * p->rl_dec[l + 1].off[B]);
+        }
+        p->decb = p->alloc((long)p->M * p->rl_dec[d.n].off[B]);
+        p->named["muls"] = p->muls;
+        p->named["dec"] = p->decb;
+        p->named["cond"] = d.cond;
+    }
     p->rag_tab = p->alloc((long)p->rag_host.size());
-    p->named["emb"] = p->emb;
-    p->named["muls"] = p->muls;
-    p->named["dec"] = p->decb;
-    p->named["cond"] = d.cond;
     plan_init_streams(p);
     *out = p;
     return 0;
@@ -2178,6 +2201,7 @@ extern "C" int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int
 
 extern "C" int avc_plan_ragged_out(const avc_plan* p, int* out_len, long* out_off) {
     if (!p || !(p->flags & AVC_PLAN_RAGGED) || !out_len || !out_off) return fail(-1, "avc_plan_ragged_out: not a ragged plan");
+    if (p->flags & AVC_PLAN_SPEAKER_ONLY) return fail(-8, "avc_plan_ragged_out: a speaker-only ragged plan converts nothing (its result is ws[\"emb\"])");
     const avc_plan::RagLevel& L = p->rl_dec[p->dec.n];
     for (int b = 0; b < p->B; ++b) {
         out_len[b] = L.T[b];
@@ -2250,11 +2274,11 @@ static int rag_enc_front(const avc_plan* p, const EncNet& e, const std::vector<a
     return 0;
 }
 
-extern "C" int avc_forward_ragged(const avc_plan* p, const float* params, const float* x, const float* x_cond, float* ws, void* stream) {
-    if (!p || !params || !x || !ws) return fail(-1, "avc_forward_ragged: null argument");
-    if (!(p->flags & AVC_PLAN_RAGGED)) return fail(-8, "avc_forward_ragged: the plan was not created by avc_plan_create_ragged");
-    if (!x_cond) x_cond = x;
-    hipStream_t s = (hipStream_t)stream;
+// The ragged forward pass.  emb != NULL (AVC_PLAN_EMB_INPUT plans): the decoder's AdaIN affine GEMM reads the caller's embeddings in
+// place (element strides seb, sec) and the speaker encoder does not run; otherwise it reads ws["emb"], the speaker encoder's result.
+static int rag_forward_impl(const avc_plan* p, const float* params, const float* x, const float* x_cond, const float* emb, long seb, long sec, float* ws,
+                            hipStream_t s) {
+    const bool do_spk = !(p->flags & AVC_PLAN_EMB_INPUT), do_enc = !(p->flags & AVC_PLAN_SPEAKER_ONLY);
     const int B = p->B;
     // tables -> workspace (a few KB; stream-ordered in front of everything that reads them)
     RUN((int)hipMemcpyAsync(ws + p->rag_tab, p->rag_host.data(), p->rag_host.size() * sizeof(int), hipMemcpyHostToDevice, s));
@@ -2277,8 +2301,10 @@ extern "C" int avc_forward_ragged(const avc_plan* p, const float* params, const 
         return a;
     };
     const hipStream_t mainS = s;
-    const hipStream_t sideS = fork_side(p, mainS);
-    {   // ---------------- speaker encoder on the target utterances (model.py:265-277)
+    // two branches: the speaker encoder runs on the side stream beside the content encoder.  A plan with one of them has nothing to overlap
+    // (and nothing to join): every kernel goes to the caller's stream
+    const hipStream_t sideS = (do_spk && do_enc) ? fork_side(p, mainS) : mainS;
+    if (do_spk) {   // ---------------- speaker encoder on the target utterances (model.py:265-277)
         const hipStream_t s = sideS;
         const EncNet& e = p->spk;
         const float SL = e.slope;
@@ -2320,7 +2346,7 @@ extern "C" int avc_forward_ragged(const avc_plan* p, const float* params, const 
         }
         RUN(avc_launch_dense(da, 0, s));
     }
-    {   // ---------------- content encoder on the source utterances (model.py:301-323)
+    if (do_enc) {   // ---------------- content encoder on the source utterances (model.py:301-323)
         const EncNet& e = p->enc;
         const float SL = e.slope;
         const std::vector<avc_plan::RagLevel>& lv = p->rl_enc;
@@ -2344,14 +2370,16 @@ extern "C" int avc_forward_ragged(const avc_plan* p, const float* params, const 
         RUN(avc_launch_conv(h, s, 0, p->tun));
     }
     join_side(p, mainS, sideS);
-    {   // ---------------- decoder(mu, emb) (model.py:347-371, :387-391: no noise)
+    if (do_enc) {   // ---------------- decoder(mu, emb) (model.py:347-371, :387-391: no noise)
         const DecNet& d = p->dec;
         const float SL = d.slope;
         const std::vector<avc_plan::RagLevel>& lv = p->rl_dec;
         const int C = d.c.c_h, Cz = d.c.c_in;
         const long csb = (long)2 * d.n * 2 * C;
-        {   // all 2n AdaIN affine Linears as ONE GEMM on emb (uniform: one row per utterance)
-            ConvArgs a = mk_fwd(p, SL, p->layers[d.affine], params, ws, ws + p->emb, 0, 1, d.c.c_cond, 1, B, ws + d.cond, 0, 1, (int)csb, 0);
+        const float* es = emb ? emb : ws + p->emb;
+        const long esb = emb ? seb : d.c.c_cond, esc = emb ? sec : 1;
+        {   // all 2n AdaIN affine Linears as ONE GEMM on emb (uniform: one row per utterance; esb = 0: every utterance reads the same row)
+            ConvArgs a = mk_fwd(p, SL, p->layers[d.affine], params, ws, es, 0, esc, (int)esb, 1, B, ws + d.cond, 0, 1, (int)csb, 0);
             RUN(avc_launch_conv(a, s, 0, p->tun));
         }
         {   // z = mu: the first Cz channels of every sample's (mu | log_sigma) block
@@ -2374,4 +2402,30 @@ extern "C" int avc_forward_ragged(const avc_plan* p, const float* params, const 
         RUN(avc_launch_conv(o, s, 0, p->tun));
     }
     return 0;
+}
+
+extern "C" int avc_forward_ragged(const avc_plan* p, const float* params, const float* x, const float* x_cond, float* ws, void* stream) {
+    if (!p || !params || !ws) return fail(-1, "avc_forward_ragged: null argument");
+    if (!(p->flags & AVC_PLAN_RAGGED)) return fail(-8, "avc_forward_ragged: the plan was not created by avc_plan_create_ragged");
+    if (p->flags & AVC_PLAN_EMB_INPUT) return fail(-8, "avc_forward_ragged: AVC_PLAN_EMB_INPUT plans run through avc_forward_ragged_emb");
+    if (p->flags & AVC_PLAN_SPEAKER_ONLY) {
+        if (!x_cond) return fail(-1, "avc_forward_ragged: a speaker-only plan reads x_cond (x is ignored), it must not be NULL");
+        return rag_forward_impl(p, params, nullptr, x_cond, nullptr, 0, 0, ws, (hipStream_t)stream);
+    }
+    if (!x) return fail(-1, "avc_forward_ragged: null argument");
+    if (!x_cond) x_cond = x;
+    return rag_forward_impl(p, params, x, x_cond, nullptr, 0, 0, ws, (hipStream_t)stream);
+}
+
+// conversion from embeddings the caller already has (an enrolled speaker, a mean, a point between two speakers)
+extern "C" int avc_forward_ragged_emb(const avc_plan* p, const float* params, const float* x, const float* emb, long seb, long sec, float* ws,
+                                      void* stream) {
+    if (!p || !params || !x || !ws) return fail(-1, "avc_forward_ragged_emb: null argument");
+    if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_EMB_INPUT))
+        return fail(-8, "avc_forward_ragged_emb: the plan was not created by avc_plan_create_ragged_ex with AVC_PLAN_EMB_INPUT");
+    if (!emb) return fail(-1, "avc_forward_ragged_emb: emb is NULL (the plan has no speaker encoder to compute it)");
+    // (the conv kernel addresses its source with 32-bit element offsets; -1 marks a structural zero)
+    if (seb < 0 || sec < 0 || (p->B - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
+        return fail(-1, "avc_forward_ragged_emb: emb strides must be non-negative and span less than 2^31 elements");
+    return rag_forward_impl(p, params, x, nullptr, emb, seb, sec, ws, (hipStream_t)stream);
 }

@@ -305,18 +305,43 @@ class Plan:
 
 
 class RaggedPlan:
-    """Launch plan of ONE forward-only pass over B (source, target) utterance pairs of DIFFERENT lengths
-    (avc_plan_create_ragged): the batched form of ``Inferencer.inference_one_utterance`` (inference.py:54-70).  Nothing is
-    padded; result b equals ``AE.inference(x_b, x_cond_b)`` (model.py:387-391)."""
+    """Launch plan of ONE forward-only pass over B utterances of DIFFERENT lengths (avc_plan_create_ragged_ex).  Nothing is padded.
 
-    def __init__(self, config, T, T_cond=None, lib=None, compute_dtype="fp32", device=None, tuning=None):
+    mode "pairs" (default): B (source, target) pairs through all three networks, the batched form of
+    ``Inferencer.inference_one_utterance`` (inference.py:54-70); result b equals ``AE.inference(x_b, x_cond_b)`` (model.py:387-391).
+    mode "speaker": only the speaker encoder, over B target utterances of lengths ``T_cond`` (``T`` is ignored and may be None):
+    ``forward(params, None, x_cond, ws)``, then ``emb(ws)`` is the [B, c_cond] result (AE.get_speaker_embeddings, model.py:393-395).
+    mode "emb": content encoder + decoder over B sources of lengths ``T`` (``T_cond`` is ignored), the speaker embeddings come from the
+    caller: ``forward_emb(params, x, emb, ws)``; result b equals ``decoder(content_encoder(x_b)[0], emb_b)``.
+    The part plans pack only their networks' weights and their workspaces are smaller; in fp32 a branch computes bit for bit what it
+    computes in the "pairs" plan over the same lengths."""
+
+    MODES = {"pairs": 0, "speaker": _lib.PLAN_SPEAKER_ONLY, "emb": _lib.PLAN_EMB_INPUT}
+
+    def __init__(self, config, T, T_cond=None, lib=None, compute_dtype="fp32", device=None, tuning=None, mode="pairs"):
         self.lib = lib if lib is not None else _lib.load()
         self.cfg = cfg_from_dict(config)
-        self.T = [int(t) for t in T]
-        self.T_cond = [int(t) for t in (T_cond if T_cond is not None else T)]
-        if len(self.T) != len(self.T_cond) or not self.T:
+        if mode not in self.MODES:
+            raise ValueError(f"mode must be one of {sorted(self.MODES)}, got {mode!r}")
+        self.mode = mode
+        if mode == "speaker":
+            if T_cond is None:
+                raise ValueError("a 'speaker' plan takes the target lengths as T_cond (T is ignored)")
+            self.T_cond = [int(t) for t in T_cond]
+            self.T = []
+            self.B = len(self.T_cond)
+        elif mode == "emb":
+            self.T = [int(t) for t in T]
+            self.T_cond = []
+            self.B = len(self.T)
+        else:
+            self.T = [int(t) for t in T]
+            self.T_cond = [int(t) for t in (T_cond if T_cond is not None else T)]
+            if len(self.T) != len(self.T_cond):
+                raise ValueError("T and T_cond must be equally long, non-empty lists")
+            self.B = len(self.T)
+        if not self.B:
             raise ValueError("T and T_cond must be equally long, non-empty lists")
-        self.B = len(self.T)
         key = str(compute_dtype).lower()
         if key not in ("fp32", "float32", "f32", "bf16", "bfloat16", "bf16r", "bf16_operands"):
             raise ValueError("ragged plans compute in fp32 or bf16 (operand rounding: the pair-storage engine takes uniform shapes)")
@@ -325,7 +350,11 @@ class RaggedPlan:
         arr = ctypes.c_int * self.B
         dev = torch.device(device) if device is not None else None
         with (torch.cuda.device(dev) if (dev is not None and dev.type == "cuda") else contextlib.nullcontext()):
-            rc = self.lib.avc_plan_create_ragged(ctypes.byref(self.cfg), self.B, arr(*self.T), arr(*self.T_cond), ctypes.byref(tun), ctypes.byref(h))
+            if mode == "pairs":
+                rc = self.lib.avc_plan_create_ragged(ctypes.byref(self.cfg), self.B, arr(*self.T), arr(*self.T_cond), ctypes.byref(tun), ctypes.byref(h))
+            else:
+                rc = self.lib.avc_plan_create_ragged_ex(ctypes.byref(self.cfg), self.B, arr(*self.T) if self.T else None,
+                                                        arr(*self.T_cond) if self.T_cond else None, self.MODES[mode], ctypes.byref(tun), ctypes.byref(h))
         if rc != 0:
             raise RuntimeError(self.lib.avc_last_error().decode())
         self.h = h
@@ -341,24 +370,58 @@ class RaggedPlan:
             off, n, dims = ctypes.c_long(), ctypes.c_long(), (ctypes.c_int * 3)()
             self.lib.avc_plan_param_info(h, i, ctypes.byref(off), ctypes.byref(n), ctypes.byref(dims))
             self.param_info.append((off.value, n.value, tuple(d for d in dims if d > 0)))
-        lens, offs = (ctypes.c_int * self.B)(), (ctypes.c_long * self.B)()
-        if self.lib.avc_plan_ragged_out(h, lens, offs) != 0:
-            raise RuntimeError(self.lib.avc_last_error().decode())
-        self.out_len, self.out_off = list(lens), list(offs)
+        self.out_len, self.out_off = [], []
+        if mode != "speaker":
+            lens, offs = (ctypes.c_int * self.B)(), (ctypes.c_long * self.B)()
+            if self.lib.avc_plan_ragged_out(h, lens, offs) != 0:
+                raise RuntimeError(self.lib.avc_last_error().decode())
+            self.out_len, self.out_off = list(lens), list(offs)
         self.n_mels = int(self.cfg.enc.c_in)
+        self.c_emb = int(self.cfg.dec.c_cond)
 
     close = Plan.close
     __del__ = Plan.__del__
     _chk = Plan._chk
+    buffer = Plan.buffer
+
+    def _rows(self, t, lens, name):
+        if t.dim() != 2 or t.shape[0] != sum(lens) or t.shape[1] != self.n_mels or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [{sum(lens)}, {self.n_mels}] tensor")
 
     def forward(self, params, x, x_cond, ws):
-        """x / x_cond: the utterances back to back as rows of frames, [sum T, M] contiguous fp32 (x_cond None = x)."""
-        if x.dim() != 2 or x.shape[0] != sum(self.T) or x.shape[1] != self.n_mels or not x.is_contiguous():
-            raise ValueError(f"x must be a contiguous [{sum(self.T)}, {self.n_mels}] tensor")
-        if x_cond is not None and (x_cond.dim() != 2 or x_cond.shape[0] != sum(self.T_cond) or x_cond.shape[1] != self.n_mels or not x_cond.is_contiguous()):
-            raise ValueError(f"x_cond must be a contiguous [{sum(self.T_cond)}, {self.n_mels}] tensor")
+        """x / x_cond: the utterances back to back as rows of frames, [sum T, M] contiguous fp32 (x_cond None = x).
+        A "speaker" plan reads x_cond only (pass x = None)."""
+        if self.mode == "emb":
+            raise RuntimeError("an 'emb' plan has no speaker encoder: call forward_emb(params, x, emb, ws)")
+        if self.mode == "speaker":
+            if x_cond is None:
+                raise ValueError("a 'speaker' plan reads x_cond: forward(params, None, x_cond, ws)")
+            self._rows(x_cond, self.T_cond, "x_cond")
+            x = None
+        else:
+            self._rows(x, self.T, "x")
+            if x_cond is not None:
+                self._rows(x_cond, self.T_cond, "x_cond")
         with _on(ws):
             self._chk(self.lib.avc_forward_ragged(self.h, _ptr(params), _ptr(x), _ptr(x_cond), _ptr(ws), _stream(ws)))
+
+    def forward_emb(self, params, x, emb, ws):
+        """"emb" plans: x as in ``forward``; emb: fp32 [B, c_cond] on the workspace's device, read in place whatever its (non-negative)
+        strides -- an ``expand``-ed [1, c_cond] row (batch stride 0) is ONE embedding for all utterances and is never materialised."""
+        if self.mode != "emb":
+            raise RuntimeError(f"forward_emb needs a plan of mode 'emb' (this one is {self.mode!r}: call forward)")
+        self._rows(x, self.T, "x")
+        if emb.dim() != 2 or tuple(emb.shape) != (self.B, self.c_emb) or emb.dtype != torch.float32 or emb.device != ws.device:
+            raise ValueError(f"emb must be an fp32 [{self.B}, {self.c_emb}] tensor on {ws.device}")
+        if emb.stride(0) < 0 or emb.stride(1) < 0:
+            emb = emb.contiguous()
+        with _on(ws):
+            self._chk(self.lib.avc_forward_ragged_emb(self.h, _ptr(params), _ptr(x), _ptr(emb), emb.stride(0), emb.stride(1), _ptr(ws), _stream(ws)))
+
+    def emb(self, ws):
+        """[B, c_cond] view of the speaker embeddings in the workspace ("pairs" and "speaker" plans)"""
+        off = self.buffer("emb")
+        return ws[off:off + self.B * self.c_emb].view(self.B, self.c_emb)
 
     def outputs(self, ws):
         """list of [M, out_len[b]] views of the converted utterances in the workspace"""

@@ -5,7 +5,8 @@ Kept from the reference: ``Inferencer(config, args)``, ``load_model`` (``args.mo
 ``<path>.ckpt`` state_dict), ``attr`` pickle with per-bin ``mean``/``std``,
 ``utt_make_frames``, ``normalize`` / ``denormalize``, ``inference_one_utterance(x, x_cond)``.
 Added: ``convert_batch`` — many (source, target) pairs of arbitrary, unequal lengths in few engine
-calls (pairs are bucketed by shape; the reference only ever runs batch 1).
+calls (pairs are bucketed by shape; the reference only ever runs batch 1); ``enroll`` + ``convert_batch(sources, emb=...)`` —
+enrol a target voice once from any number of utterances, then convert whatever comes in without running the speaker encoder again.
 
 The audio front and back end (reference: ``get_spectrograms`` / ``melspectrogram2wav`` of
 ``preprocess/tacotron/utils.py``, librosa on the CPU there) run on the GPU through ``dsp.MelDSP``:
@@ -95,27 +96,61 @@ class Inferencer(object):
         from scipy.io.wavfile import write
         write(output_path, rate=int(getattr(self.args, "sample_rate", 24000)), data=wav_data)
 
+    def _mel_from_path(self, path):
+        mel, _ = self.dsp().get_spectrograms(path)
+        return torch.from_numpy(self.normalize(mel)).float()
+
     def inference_from_path(self):
+        """The reference's command (one ``-source``, one ``-target``), and the enrolment workflow on top of it: several targets
+        (``args.target`` a list: the voice is the mean embedding of the files), ``args.save_emb`` (write the enrolled embedding with
+        ``torch.save``; without ``args.source`` nothing is converted), ``args.emb`` (convert with a saved embedding instead of a target)."""
         dsp = self.dsp()
         if self.model._n_mels != dsp.hp.n_mels:
             raise ValueError(f"the model works on {self.model._n_mels}-mel features, get_spectrograms produces {dsp.hp.n_mels} "
                              "(preprocess/tacotron/hyperparams.py:29)")
-        src_mel, _ = dsp.get_spectrograms(self.args.source)
-        tar_mel, _ = dsp.get_spectrograms(self.args.target)
-        src_mel = torch.from_numpy(self.normalize(src_mel)).float()
-        tar_mel = torch.from_numpy(self.normalize(tar_mel)).float()
-        conv_wav, conv_mel = self.inference_one_utterance(src_mel, tar_mel)
+        target = getattr(self.args, "target", None)
+        targets = list(target) if isinstance(target, (list, tuple)) else ([target] if target is not None else [])
+        emb_path, save_emb = getattr(self.args, "emb", None), getattr(self.args, "save_emb", None)
+        if emb_path is not None and targets:
+            raise ValueError("give either -target (one or several wav files to enrol from) or -emb (a saved embedding), not both")
+        if emb_path is None and not targets:
+            raise ValueError("a target voice is needed: -target (one or several wav files) or -emb (a saved embedding)")
+        if len(targets) == 1 and emb_path is None and save_emb is None:   # the reference's path (inference.py:86-93)
+            conv_wav, conv_mel = self.inference_one_utterance(self._mel_from_path(self.args.source), self._mel_from_path(targets[0]))
+            self.write_wav_to_file(conv_wav, self.args.output)
+            return conv_wav, conv_mel
+        if emb_path is not None:
+            emb = torch.load(emb_path, map_location="cpu")
+        else:
+            emb = self.enroll([self._mel_from_path(t) for t in targets])
+        if save_emb is not None:
+            torch.save(emb.detach().cpu(), save_emb)
+        if getattr(self.args, "source", None) is None:
+            return None, None   # enrolment only
+        conv_mel = self.denormalize(self.convert_batch([self._mel_from_path(self.args.source)], emb=emb)[0].numpy())
+        conv_wav = self.mel2wav(conv_mel) if self.mel2wav is not None else dsp.melspectrogram2wav(conv_mel)
         self.write_wav_to_file(conv_wav, self.args.output)
         return conv_wav, conv_mel
 
-    def convert_batch_to_wav(self, pairs, max_streams=4, do_trim=True, n_iter=None):
+    def enroll(self, utterances):
+        """Enrol a target voice: ``utterances`` are normalised [T, M] mels of ONE speaker, of any (unequal) lengths.  All of them go
+        through the speaker encoder in ONE ragged launch set (``AE.get_speaker_embeddings_ragged``); returns the mean of their
+        embeddings, [c_emb], on the model's device -- what ``convert_batch(sources, emb=...)`` takes."""
+        utterances = list(utterances)
+        if not utterances:
+            raise ValueError("enroll: at least one utterance is needed")
+        with torch.no_grad():
+            return self.model.get_speaker_embeddings_ragged(utterances).mean(0)
+
+    def convert_batch_to_wav(self, pairs, max_streams=4, do_trim=True, n_iter=None, emb=None):
         """`convert_batch` + the audio back end: the converted mels are denormalised (inference.py:68) and vocoded by
         `melspectrogram2wav` -- all utterances, whatever their lengths, in ONE batched Griffin-Lim launch set (dsp.MelDSP).
+        ``emb``: as in ``convert_batch`` (``pairs`` is then the list of sources).
         Returns (list of float32 waveforms, list of converted mels) in input order."""
-        mels = [self.denormalize(m.numpy()) for m in self.convert_batch(pairs, max_streams)]
+        mels = [self.denormalize(m.numpy()) for m in self.convert_batch(pairs, max_streams, emb=emb)]
         return self.dsp().melspectrogram2wav_batch(mels, do_trim=do_trim, n_iter=n_iter), mels   # ONE Griffin-Lim launch set, any lengths
 
-    def convert_batch(self, pairs, max_streams=4, ragged=True):
+    def convert_batch(self, pairs, max_streams=4, ragged=True, emb=None):
         """pairs: list of (src [T,M], tgt [T',M]) tensors of any lengths.  Default: ONE ragged launch set over all pairs
         (``AE.inference_ragged``: per-sample lengths inside every kernel; real utterances all differ in length, so shape buckets
         would be batches of one).  ``ragged=False``: the round-2 path -- pairs with equal (T, T') share one uniform plan,
@@ -123,7 +158,19 @@ class Inferencer(object):
         InstanceNorm statistics depend on the true length, so padding would change the result.
         Under ``compute_dtype: bf16`` the ragged path rounds the matrix-product operands to bf16 on fp32 storage ("bf16r"; the bf16
         pair-STORAGE engine of ``AE.inference`` takes uniform shapes only) -- ``self.model.last_ragged_compute`` says which mode ran.
+        ``emb`` (an enrolled voice: ``enroll``'s result, [c_emb]; or one embedding per source, [B, c_emb]): ``pairs`` is then the list
+        of SOURCES ([T,M] tensors) alone, converted to that voice in one ragged launch set in which the speaker encoder does not run
+        (``AE.inference_ragged(xs, emb=...)``).
         Returns the converted mels ([T'',M] CPU tensors) in input order."""
+        if emb is not None:
+            if not ragged:
+                raise ValueError("convert_batch(sources, emb=...) runs the ragged plan; ragged=False converts (source, target) pairs")
+            srcs = list(pairs)
+            if any(isinstance(s, (tuple, list)) for s in srcs):
+                raise ValueError("convert_batch(sources, emb=...): pass the source utterances alone ([T, M] tensors), not (source, target) pairs")
+            with torch.no_grad():
+                outs = self.model.inference_ragged(srcs, emb=emb)
+            return [o.t().cpu() for o in outs]
         if ragged:
             with torch.no_grad():
                 outs = self.model.inference_ragged([s for s, _ in pairs], [t for _, t in pairs])
@@ -165,19 +212,35 @@ class Inferencer(object):
         return out
 
 
-def main(argv=None):
-    """The reference's command line (inference.py:95-109)."""
+def make_parser():
+    """The reference's command line (inference.py:95-109) plus the enrolment options."""
     from argparse import ArgumentParser
-    from .config import load_config
     parser = ArgumentParser()
     parser.add_argument('-attr', '-a', help='attr file path')
     parser.add_argument('-config', '-c', help='config file path')
     parser.add_argument('-model', '-m', help='model path')
     parser.add_argument('-source', '-s', help='source wav path')
-    parser.add_argument('-target', '-t', help='target wav path')
+    parser.add_argument('-target', '-t', action='append',
+                        help='target wav path; may be given several times: the voice is then enrolled from all of them (mean embedding)')
     parser.add_argument('-output', '-o', help='output wav path')
     parser.add_argument('-sample_rate', '-sr', help='sample rate', default=24000, type=int)
-    args = parser.parse_args(argv)
+    parser.add_argument('-save_emb', help='write the enrolled speaker embedding here (torch.save); without -source nothing is converted')
+    parser.add_argument('-emb', help='convert with a speaker embedding saved by -save_emb instead of -target')
+    return parser
+
+
+def parse_args(argv=None):
+    """A single -target stays the string it has always been; several become a list."""
+    args = make_parser().parse_args(argv)
+    if args.target is not None and len(args.target) == 1:
+        args.target = args.target[0]
+    return args
+
+
+def main(argv=None):
+    """The reference's command line (inference.py:95-109)."""
+    from .config import load_config
+    args = parse_args(argv)
     inferencer = Inferencer(config=load_config(args.config), args=args)
     inferencer.inference_from_path()
 

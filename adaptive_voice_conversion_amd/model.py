@@ -413,7 +413,7 @@ class AE(nn.Module):
                                   "content": 4, "decoder": 4, "speaker_train": 2, "content_train": 2, "decoder_train": 2,
                                   # ... and the plans whose backward also computes the inputs' gradients (inputs that require grad)
                                   "ig_train": 2, "speaker_ig_train": 2, "content_ig_train": 2})
-        self._ragged = {}   # (lengths, device) -> (RaggedPlan, None), a few most recent
+        self._ragged = {}   # (mode, lengths, device) -> (RaggedPlan, None), a few most recent; mode: "pairs" | "speaker" | "emb"
         self._ragged_ws = None   # the one workspace they share
         self.last_ragged_compute = None
 
@@ -545,20 +545,17 @@ class AE(nn.Module):
         plan.forward(self._flat, x, x_cond, None, ws)
         return self._outputs(plan, ws)[2].clone()
 
-    def inference_ragged(self, xs, x_conds):
-        """Batched ``inference`` over utterances of DIFFERENT lengths in ONE launch set (engine.RaggedPlan; the reference converts
-        one utterance per call, inference.py:62-70).  xs / x_conds: lists of [T_b, M] / [T'_b, M] tensors (frames as rows -- what
-        ``utt_make_frames`` views); returns the list of converted [M, T''_b] tensors, result b == inference(x_b, x_cond_b)."""
+    def _ragged_plan(self, mode, T, Tc):
+        """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all three modes are kept."""
         from .engine import RaggedPlan
         dev = self._flat.device
-        T, Tc = tuple(int(x.shape[0]) for x in xs), tuple(int(x.shape[0]) for x in x_conds)
-        key = (T, Tc, str(dev))
+        key = (mode, T, Tc, str(dev))
         hit = self._ragged.get(key)
         if hit is None:
             # compute_dtype "bf16" -> "bf16r" here: the pair-STORAGE engine takes uniform shapes only; ragged plans round the operands of
             # the matrix products to bf16 on fp32 storage (engine.RaggedPlan).  The mode that ran is reported in `last_ragged_compute`.
             plan = RaggedPlan(self.config, T, Tc, lib=self._lib, compute_dtype="bf16r" if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")) else "fp32", device=dev,
-                              tuning=self._tuning)
+                              tuning=self._tuning, mode=mode)
             if [(o, n) for o, n, _ in plan.param_info] != [(o, n) for o, n, _ in self._layout]:
                 raise RuntimeError("flat parameter layout of the C plan differs from the module's")
             hit = self._ragged[key] = (plan, None)
@@ -574,10 +571,66 @@ class AE(nn.Module):
         if ws is None or ws.device != dev or ws.numel() < plan.workspace_floats:
             ws = self._ragged_ws = torch.zeros(int(plan.workspace_floats * 1.25) + 1024, dtype=torch.float32, device=dev)
         self.last_ragged_compute = plan.compute_dtype
-        x = torch.cat([self._prep(t).to(dev) for t in xs]).contiguous()
-        xc = torch.cat([self._prep(t).to(dev) for t in x_conds]).contiguous()
-        plan.forward(self._flat, x, xc, ws)
+        return plan, ws
+
+    def _ragged_rows(self, ts, name):
+        dev = self._flat.device
+        ts = list(ts)
+        if not ts:
+            raise ValueError(f"{name}: an empty list of utterances")
+        for t in ts:
+            if t.dim() != 2 or t.shape[1] != self._n_mels:
+                raise ValueError(f"{name}: every utterance must be a [T, {self._n_mels}] tensor (frames as rows), got {tuple(t.shape)}")
+        return tuple(int(t.shape[0]) for t in ts), torch.cat([self._prep(t).to(dev) for t in ts]).contiguous()
+
+    def inference_ragged(self, xs, x_conds=None, emb=None):
+        """Batched ``inference`` over utterances of DIFFERENT lengths in ONE launch set (engine.RaggedPlan; the reference converts
+        one utterance per call, inference.py:62-70).  xs / x_conds: lists of [T_b, M] / [T'_b, M] tensors (frames as rows -- what
+        ``utt_make_frames`` views); returns the list of converted [M, T''_b] tensors, result b == inference(x_b, x_cond_b).
+
+        Exactly one of ``x_conds`` and ``emb``.  ``emb``: speaker embeddings the caller already has (``get_speaker_embeddings_ragged``,
+        a mean over enrolment utterances, a point between two speakers) -- [B, c_emb], one row per source, or [c_emb] / [1, c_emb]: one
+        voice for all sources (read with batch stride 0, never expanded in memory).  The speaker encoder then does not run at all;
+        result b == decoder(content_encoder(x_b)[0], emb_b), bit-identical in fp32 to the ``x_conds`` call those embeddings came from.
+        Forward only, like the ``x_conds`` form: an ``emb`` that requires grad is refused while grad is enabled."""
+        if (x_conds is None) == (emb is None):
+            raise ValueError("inference_ragged: pass exactly one of x_conds (a list of target utterances, [T'_b, M] each) and "
+                             "emb (speaker embeddings, [B, c_emb] or [c_emb])")
+        if emb is None:
+            T, x = self._ragged_rows(xs, "xs")
+            Tc, xc = self._ragged_rows(x_conds, "x_conds")
+            if len(T) != len(Tc):
+                raise ValueError(f"inference_ragged: {len(T)} sources but {len(Tc)} targets")
+            plan, ws = self._ragged_plan("pairs", T, Tc)
+            plan.forward(self._flat, x, xc, ws)
+            return [o.clone() for o in plan.outputs(ws)]
+        if not torch.is_tensor(emb):
+            raise ValueError(f"inference_ragged: emb must be a tensor of shape [B, {self._c_emb}] or [{self._c_emb}]")
+        if torch.is_grad_enabled() and emb.requires_grad:
+            raise RuntimeError("inference_ragged is forward-only: emb requires grad and its gradient would be lost.  Use the differentiable "
+                               "uniform path decoder(z, cond) -- ae.decoder(ae.content_encoder(x)[0], emb) -- or pass emb.detach()")
+        T, x = self._ragged_rows(xs, "xs")
+        B, C = len(T), self._c_emb
+        e = self._prep(emb.detach()).to(self._flat.device)
+        if e.dim() == 1 and e.shape[0] == C:
+            e = e[None]
+        if e.dim() != 2 or e.shape[1] != C or e.shape[0] not in (1, B):
+            raise ValueError(f"inference_ragged: emb must be [{B}, {C}] (one row per source), or [{C}] / [1, {C}] (one voice for all "
+                             f"{B} sources); got {tuple(emb.shape)}")
+        if e.shape[0] == 1:
+            e = e.expand(B, C)   # batch stride 0: the engine reads the one row B times
+        plan, ws = self._ragged_plan("emb", T, ())
+        plan.forward_emb(self._flat, x, e, ws)
         return [o.clone() for o in plan.outputs(ws)]
+
+    def get_speaker_embeddings_ragged(self, x_conds):
+        """``get_speaker_embeddings`` (model.py:393-395) over utterances of DIFFERENT lengths in ONE launch set: x_conds is a list of
+        [T'_b, M] tensors (frames as rows, the layout ``inference_ragged`` takes); returns [B, c_emb], row b ==
+        get_speaker_embeddings(x_cond_b).  Only the speaker encoder runs (a "speaker" RaggedPlan).  Forward only."""
+        Tc, xc = self._ragged_rows(x_conds, "x_conds")
+        plan, ws = self._ragged_plan("speaker", (), Tc)
+        plan.forward(self._flat, None, xc, ws)
+        return plan.emb(ws).clone()
 
     # ---- the three networks called on their own (SpeakerEncoder / ContentEncoder / Decoder.forward) --------
     def _part_grad(self, part, *inputs):

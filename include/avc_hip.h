@@ -19,8 +19,9 @@
  *      (1) avc_plan_create* allocates a small DEVICE table (hipMalloc: the weight-image descriptors of avc_plan_pack_weights, a few KB)
  *          and fills it with a blocking hipMemcpy; avc_plan_destroy frees it.  Create plans outside captured / latency-critical regions.
  *      (2) the FIRST plan created on a device creates that device's three helper HIP streams (below); they live until the process ends.
- *      (3) avc_forward_ragged uploads its per-utterance length / offset / tile tables (a few KB) with hipMemcpyAsync from pageable host
- *          memory: the call may block the host until the copy is staged and is NOT graph-capture safe (the uniform entry points are).
+ *      (3) avc_forward_ragged and avc_forward_ragged_emb upload their per-utterance length / offset / tile tables (a few KB) with
+ *          hipMemcpyAsync from pageable host memory: the call may block the host until the copy is staged and is NOT graph-capture safe
+ *          (the uniform entry points are).
  *  - return value: 0 = ok, < 0 = bad argument / unsupported shape,
  *    > 0 = hipError_t.  avc_last_error() describes the last failure.
  *  - the stream is always an argument (backward runs on PyTorch's autograd
@@ -271,6 +272,25 @@ int avc_forward_ex(const avc_plan* p, const float* params, const float* x, long 
 int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, const avc_tuning* tuning, avc_plan** out);
 int avc_plan_ragged_out(const avc_plan* p, int* out_len, long* out_off);
 int avc_forward_ragged(const avc_plan* p, const float* params, const float* x, const float* x_cond, float* ws, void* stream);
+/* RAGGED PART PLANS (enrol a speaker once, convert from the embedding): avc_plan_create_ragged is avc_plan_create_ragged_ex with
+ * flags = 0.  At most ONE of the two flags below; any other bit is refused.  Either plan packs only the weight images of the networks it
+ * runs and allocates only their buffers and tables (avc_plan_workspace_floats is smaller than the whole ragged plan's), takes the full
+ * flat parameter buffer, honours avc_plan_set_compute_dtype as a whole ragged plan does, and checks the reflect-pad rule for the
+ * networks it runs only.  A branch runs the SAME kernel instances as in the whole ragged plan over the same lengths (the launch choice
+ * is a function of the layer and of its own level tables only): in fp32 the results are bit-identical to the whole plan's.
+ *  - AVC_PLAN_SPEAKER_ONLY: only the speaker encoder runs, over T_cond[0..B) (T is ignored and may be NULL).
+ *    avc_forward_ragged(p, params, NULL, x_cond, ws, stream) leaves ws["emb"] [B, c_cond] fp32 contiguous; x_cond must not be NULL.
+ *    One branch, one stream: every kernel goes to the caller's stream.  avc_plan_ragged_out is refused (there is no "dec").
+ *  - AVC_PLAN_EMB_INPUT: the speaker encoder does not run (T_cond is ignored and may be NULL); the content encoder and the decoder run
+ *    through avc_forward_ragged_emb, with the caller's embeddings in place of the speaker encoder's: emb is [B, c_cond] fp32 on the
+ *    device, read in place with non-negative element strides (seb, sec) as avc_decoder_forward reads its emb.  seb = 0 is legal: ONE
+ *    embedding for all B utterances.  Results are where a whole ragged plan leaves them (avc_plan_ragged_out, ws["dec"], ws["muls"]).
+ *    avc_forward_ragged is refused on such a plan, avc_forward_ragged_emb on every other plan. */
+#define AVC_PLAN_EMB_INPUT 512
+int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, int flags, const avc_tuning* tuning,
+                              avc_plan** out);
+int avc_forward_ragged_emb(const avc_plan* p, const float* params, const float* x, const float* emb, long seb, long sec, float* ws,
+                           void* stream);
 
 /* L1 + KL losses of solver.py:84-86 -> ws["losses"] = {loss_rec, loss_kl}; writes
  * d(lambda_rec*loss_rec)/d(dec) into ws["d_dec"] for avc_backward. */
