@@ -90,6 +90,8 @@ def declare(lib):
         lib.avc_plan_create_ragged_ex.argtypes = [ctypes.POINTER(ModelCfg), c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
                                                   ctypes.POINTER(Tuning), ctypes.POINTER(c_void_p)]
         lib.avc_forward_ragged_emb.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]
+    if hasattr(lib, "avc_backward_ragged"):   # (likewise)
+        lib.avc_backward_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]
     lib.avc_gather_segments.argtypes = [c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.avc_plan_destroy.argtypes = [c_void_p]
     lib.avc_plan_destroy.restype = None

@@ -76,7 +76,12 @@ struct ConvRag {
     const int* offres;
     int cx, cout, cres;   // channels per sample of the packed source / output / residual buffers
     int ntiles;
+    int xc0;              // first channel of the source rows inside the sample's block (input gradient of one conv-bank member: its slice of d(cat))
 };
+// Ragged INPUT-GRADIENT launches (mode 1; avc_backward_ragged) use the same tables: Tsrc / offsrc describe the packed dy, Tout / offout
+// the packed dx -- one column tile = 64 frames of ONE sample's dx --, Tres / offres the gradient joined through the residual path (another
+// level's packed buffer).  A launch with ConvArgs.oc != 0 stores with the caller's strides (oc, ot) -- and reads its residual with
+// (rc, rt) -- inside the sample's block instead of [channels][T_b] rows: d(x_cond) leaves in the input's own [T_b][M] layout.
 
 // InstanceNorm1d(affine=False) + AdaIN affine + activation + residual join of the conv's OUTPUT rows, inside the conv epilogue (round 5):
 // for output rows of 16 / 32 / 64 frames a 64-column tile holds whole rows of whole samples, so the statistics need no second kernel

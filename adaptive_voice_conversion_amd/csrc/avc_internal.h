@@ -71,6 +71,9 @@ int avc_launch_rag_in_fwd(const RagINArgs& a, hipStream_t s);
 int avc_launch_rag_copy_rows(const float* x, long xsc, long xst, const int* T, const int* off, int B, int M, int sumT, float* dst, int CC, int c0,
                              hipStream_t s);
 int avc_launch_rag_timepool_fwd(const float* in, const int* T, const int* off, int B, int C, float* out, hipStream_t s);
+int avc_launch_rag_timepool_bwd(const float* dP, const float* amask, const int* T, const int* off, int B, int C, int sumT, float* G, float* dy,
+                                float slope, hipStream_t s);
+int avc_launch_transpose_strided(float* dst, const float* src, long sr, long sc, int R, int C, hipStream_t s);   // dst[c][r] = src[r sr + c sc]
 int avc_launch_copy_rows(const float* x, long sxb, long sxc, int sxt, int B, int M, int T, float* dst, long db, long dc,
                          hipStream_t s);
 int avc_launch_timepool_fwd(const float* in, int B, int C, int T, float* out, hipStream_t s);

@@ -201,8 +201,11 @@ static __device__ __forceinline__ void conv_chunk_mma(f32x16 (&acc)[WM][WN], con
 // wave a serial chain of 320 MFMAs).  KG groups of 4 waves work on the SAME output tile; group kg
 // runs its own double-buffered pipeline over chunks kg, kg+KG, ... and the groups' accumulators are
 // summed through LDS in a fixed order at the end (deterministic).
-// RAG (forward only): ragged launch -- the tile's sample, first column and the sample's own lengths / packed-buffer bases come
-// from the ConvRag tables; everything else is the uniform kernel with one sample per tile.
+// RAG: ragged launch -- the tile's sample, first column and the sample's own lengths / packed-buffer bases come
+// from the ConvRag tables; everything else is the uniform kernel with one sample per tile.  Input-gradient instances (mode 1; MIRROR and
+// PAR as for uniform launches): the tile is 64 frames of one sample's dx; the zero-upsampling test, the reflect-adjoint windows and the
+// ceil-mode pool adjoint of the residual join all see the sample's OWN Tsrc / Tout (T_{l+1} = ceil(T_l / 2): an odd row's last frame
+// meets dy[Tsrc - 1] through tap parity like any other, and is the pool's clipped window of weight 1).
 // WN = 2 (64 x 128 and 128 x 128 tiles; uniform stride-1 launches): two 32-column fragments per wave share every weight fragment --
 // the weight image is 80 % of a chunk's LDS-DMA bytes and it is re-read by every column tile (section 3.1 of DESIGN.md).
 // TILE WALK (round 5; WALK instances: uniform launches with KG == 1): a workgroup is PERSISTENT over `a.walk_n` column tiles of its row slab -- tiles
@@ -254,18 +257,22 @@ __global__ void __launch_bounds__(AVC_THREADS * KG) conv_gemm_kernel(const ConvA
         Bv = 1;
         xsb = 0;
         xsc = a.x.sc < 0 ? Tsrc : a.x.sc;   // packed activations: channel rows of the sample's own length; (the packed input brings explicit strides)
-        xptr += (long)a.rag.cx * a.rag.offsrc[rb_];
+        xptr += (long)a.rag.cx * a.rag.offsrc[rb_] + (long)a.rag.xc0 * xsc;
         q.b0 = 0; q.t0 = rt0; q.SPT = 1; q.ncols = BN;
-        q.SEG = (BN - 1) * a.stride + KS; q.seg_p0 = rt0 * a.stride;
+        if (a.mode == 0) {
+            q.SEG = (BN - 1) * a.stride + KS; q.seg_p0 = rt0 * a.stride;
+        } else {   // (conv_geom's input-gradient row: the main window and both mirror windows)
+            q.SEG = BN + 3 * (KS - 1); q.seg_p0 = rt0;
+        }
         q.ROWDATA = q.SEG; q.ROW = q.SEG + KS;
         epi.Tout = Tout;
         epi.ob = 0;
-        epi.oc = (long)a.ops * Tout;
+        epi.oc = a.oc ? a.oc : (long)a.ops * Tout;   // (a.oc != 0: the caller's strides inside the sample's block, see ConvRag)
         epi.obase = (long)a.rag.cout * a.rag.offout[rb_] + (long)g.out_c0 * epi.oc;
         if (a.res_mode != AVC_RES_NONE) {
             epi.Tres = a.rag.Tres[rb_];
             epi.rb = 0;
-            epi.rc = epi.Tres;
+            epi.rc = a.oc ? a.rc : epi.Tres;
             epi.rbase = (long)a.rag.cres * a.rag.offres[rb_];
         }
     } else {
@@ -328,7 +335,7 @@ __global__ void __launch_bounds__(AVC_THREADS * KG) conv_gemm_kernel(const ConvA
         int bl, t;
         bool v;
         if (PAR) {   // (WN == 1) wave_n = parity of the wave's columns, li = slot inside the parity class
-            if (Tout >= BN) {
+            if (RAG || Tout >= BN) {
                 bl = 0;
                 t = q.t0 + 2 * li + wave_n;
                 v = (t < Tout) && (q.b0 < Bv);
@@ -930,13 +937,23 @@ static int conv_ntiles_n(const ConvArgs& a, int BN) {
     return worst;
 }
 
-// ragged forward launches (inference): the straight-line instances the model uses + the generic one
+// ragged launches: the straight-line instances the model uses + the generic one (forward, and the input gradients that need no
+// reflect-adjoint window: the 1x1 convs)
 template <int WM, int BF>
 static void conv_launch_rag(const ConvArgs& a, int fast, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
     if (fast == 1) hipLaunchKernelGGL((conv_gemm_kernel<WM, 1, false, 5, 1, 1, BF, false, true>), grid, block, lds, stream, a);
     else if (fast == -1) hipLaunchKernelGGL((conv_gemm_kernel<WM, 1, false, -1, 0, 1, BF, false, true>), grid, block, lds, stream, a);
     else if (fast == 14) hipLaunchKernelGGL((conv_gemm_kernel<WM, 1, false, 1, 4, 1, BF, false, true>), grid, block, lds, stream, a);
     else hipLaunchKernelGGL((conv_gemm_kernel<WM, 1, false, 0, 0, 1, BF, false, true>), grid, block, lds, stream, a);
+}
+
+// ragged input-gradient launches with reflect-adjoint windows (exact fp32): the k = 5 straight-line chunk, with the stride-2 column-parity
+// split, and the generic chunk loop (the conv bank's widths, other kernel sizes); 64 x 64 tiles (a ragged launch is one sample per tile:
+// the launcher never picks another)
+static void conv_launch_rag_dgrad(const ConvArgs& a, int fast, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+    if (a.par && fast == 1) hipLaunchKernelGGL((conv_gemm_kernel<1, 1, true, 5, 1, 1, 0, true, true>), grid, block, lds, stream, a);
+    else if (fast == 1) hipLaunchKernelGGL((conv_gemm_kernel<1, 1, true, 5, 1, 1, 0, false, true>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((conv_gemm_kernel<1, 1, true, 0, 0, 1, 0, false, true>), grid, block, lds, stream, a);
 }
 
 template <int WM, int KG, int BF>
@@ -1085,7 +1102,8 @@ int avc_launch_conv(const ConvArgs& a_in, hipStream_t stream, int force_tile, co
     }
     size_t lds = conv_lds_bytes(a, BM, BN);
     const bool rag = a.rag.tile != nullptr;
-    if (rag && (a.mode != 0 || a.Tout < BN || a.rag.ntiles < 1)) return -2;   // (ragged launches: forward only; the caller passes Tout >= 64 for the geometry)
+    if (rag && (a.Tout < BN || a.rag.ntiles < 1)) return -2;   // (ragged launches: the caller passes Tout >= 64 for the geometry)
+    if (rag && a.mode == 1 && (a.bf16 != AVC_COMPUTE_F32 || tile == 12 || a.ngroups != 1)) return -2;   // (ragged input gradients: exact fp32, one layer per launch)
     dim3 grid(rag ? a.rag.ntiles : conv_ntiles_n(a, BN), a.Mp / BM, a.ngroups);
     // split-K groups: only where the grid leaves CUs or SIMD slots idle (<= 1 workgroup per CU)
     int kgroups = 1;
@@ -1110,7 +1128,7 @@ int avc_launch_conv(const ConvArgs& a_in, hipStream_t stream, int force_tile, co
     if (bf == 2 && (a.img != AVC_IMG_K4H || a.x.ps != 1 || a.x.st != 1)) return -2;   // bf16 pair tensors: time-contiguous dword rows, pair weight image
     if (a.pairs && (bf != 2 || a.ops != 1 || a.ot != 1 || (a.M & 1) || (a.res_mode != AVC_RES_NONE && a.rt != 1))) return -2;
     a.par = tun.dgrad_par && a.mode == 1 && a.stride == 2 && tile == 11 && a.ngroups == 1 && (fast == 1 || fast == 2) && !a.dbg &&
-            a.g[0].padL == 2 && (a.Tout >= 64 || (a.Tout % 2 == 0 && 64 % a.Tout == 0));
+            a.g[0].padL == 2 && (a.Tout >= 64 || (a.Tout % 2 == 0 && 64 % a.Tout == 0)) && !(rag && fast != 1);
     // ---- tile walk: persistent workgroups over the column tiles of a row slab (conv_gemm_kernel).  Only where every tile of a walk has
     // the geometry of the first one: rows of >= 64 frames (a walker keeps its first frame), or whole groups of short samples
     a.walk_n = 1;
@@ -1157,6 +1175,11 @@ int avc_launch_conv(const ConvArgs& a_in, hipStream_t stream, int force_tile, co
         if (!conv_launch_walk(a, tile, mir, fast, grid, block, lds, stream)) return -2;
     } else if (rag) {
         if (bf == 2) return -2;   // (ragged plans run fp32 storage)
+        if (mir) {
+            if (tile != 11) return -2;
+            conv_launch_rag_dgrad(a, fast, grid, block, lds, stream);
+            return (int)hipGetLastError();
+        }
         const int f = (fast == 1 || fast == -1 || fast == 14) ? fast : 0;
 #define AVC_C_RAG2(BF_) conv_launch_rag<2, BF_>(a, f, grid, block, lds, stream)
 #define AVC_C_RAG1(BF_) conv_launch_rag<1, BF_>(a, f, grid, block, lds, stream)

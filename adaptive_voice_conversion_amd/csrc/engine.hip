@@ -2018,10 +2018,14 @@ extern "C" int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int
 // does not run keeps its entries of the flat parameter buffer, and gets no weight image, no level table and no buffer.
 extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, int flags, const avc_tuning* tuning,
                                          avc_plan** out) {
-    if (flags & ~(AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_EMB_INPUT))
-        return fail(-1, "avc_plan_create_ragged_ex: unknown flag (ragged plans take AVC_PLAN_SPEAKER_ONLY or AVC_PLAN_EMB_INPUT)");
+    if (flags & ~(AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_EMB_INPUT | AVC_PLAN_INPUT_GRADS))
+        return fail(-1, "avc_plan_create_ragged_ex: unknown flag (ragged plans take AVC_PLAN_SPEAKER_ONLY [| AVC_PLAN_INPUT_GRADS] or AVC_PLAN_EMB_INPUT)");
     if ((flags & AVC_PLAN_SPEAKER_ONLY) && (flags & AVC_PLAN_EMB_INPUT))
         return fail(-1, "avc_plan_create_ragged_ex: AVC_PLAN_SPEAKER_ONLY and AVC_PLAN_EMB_INPUT exclude each other");
+    if ((flags & AVC_PLAN_INPUT_GRADS) && !(flags & AVC_PLAN_SPEAKER_ONLY))
+        return fail(-1, "avc_plan_create_ragged_ex: unknown flag for this ragged plan: AVC_PLAN_INPUT_GRADS is supported on ragged speaker plans only, pass AVC_PLAN_SPEAKER_ONLY | "
+                        "AVC_PLAN_INPUT_GRADS (the ragged content encoder and decoder have no backward pass; use uniform plans for their gradients)");
+    const bool ig = (flags & AVC_PLAN_INPUT_GRADS) != 0;
     const bool do_spk = !(flags & AVC_PLAN_EMB_INPUT), do_enc = !(flags & AVC_PLAN_SPEAKER_ONLY), do_dec = do_enc;
     if (!do_enc) T = T_cond;   // (speaker-only: T is ignored; the shared length checks below then read T_cond twice)
     if (!cfg || !out || !T || B < 1) return fail(-1, "avc_plan_create_ragged: bad arguments");
@@ -2116,19 +2120,30 @@ extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const 
     for (EncNet* e : {&p->spk, &p->enc}) {
         if (!(e == &p->spk ? do_spk : do_enc)) continue;
         const std::vector<avc_plan::RagLevel>& lv = (e == &p->spk) ? p->rl_spk : p->rl_enc;
-        for (int id : e->bank) finish_layer(p, p->layers[id], false, 0, lv[0].ntiles, 64, 64, e->nb);
-        finish_layer(p, p->layers[e->in_conv], false, 0, lv[0].ntiles, 64, 64);
+        // (AVC_PLAN_INPUT_GRADS -- speaker plans only -- adds the input-gradient images: transposed, tap-flipped)
+        for (int id : e->bank) finish_layer(p, p->layers[id], ig, 0, lv[0].ntiles, 64, 64, e->nb);
+        finish_layer(p, p->layers[e->in_conv], ig, e->CC - e->c.c_in, lv[0].ntiles, 64, 64);
+        if (ig) {   // the in_conv's input gradient for its last M input rows (x itself, model.py:90): w[0] rows [nb c_bank, CC)
+            LayerP L = p->layers[e->in_conv];
+            L.src_off = (long)e->nb * e->c.c_bank;
+            L.wpf = L.wrs_f = L.wrs_d = L.wplain = L.bpk = -1;
+            L.dgM = e->c.c_in;
+            L.Mp_d = avc_cdiv(L.dgM, 128) * 128;
+            L.wpd = p->alloc((long)L.nchunk_d * L.KS * L.CKd * L.Mp_d);
+            p->layers.push_back(L);
+            e->in_pass = (int)p->layers.size() - 1;
+        }
         for (int l = 0; l < e->n; ++l) {
-            finish_layer(p, p->layers[e->c1[l]], false, 0, lv[l].ntiles, 64, 64);
-            finish_layer(p, p->layers[e->c2[l]], false, 0, lv[l + 1].ntiles, 64, 64);
+            finish_layer(p, p->layers[e->c1[l]], ig, 0, lv[l].ntiles, 64, 64);
+            finish_layer(p, p->layers[e->c2[l]], ig, 0, lv[l + 1].ntiles, 64, 64);
         }
     }
     if (do_spk) {
         for (int l = 0; l < p->spk.nd; ++l) {
-            finish_layer(p, p->layers[p->spk.dn1[l]], false, 0, 1, B, B, 1, false);
-            finish_layer(p, p->layers[p->spk.dn2[l]], false, 0, 1, B, B, 1, false);
+            finish_layer(p, p->layers[p->spk.dn1[l]], ig, 0, 1, B, B, 1, false);
+            finish_layer(p, p->layers[p->spk.dn2[l]], ig, 0, 1, B, B, 1, false);
         }
-        finish_layer(p, p->layers[p->spk.outl], false, 0, 1, B, B, 1, false);
+        finish_layer(p, p->layers[p->spk.outl], ig, 0, 1, B, B, 1, false);
     }
     if (do_enc) {
         finish_layer(p, p->layers[p->enc.heads], false, 0, p->rl_dec[0].ntiles, 64, 64);
@@ -2175,6 +2190,31 @@ extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const 
         alloc_enc(p->spk, p->rl_spk, true);
         p->emb = p->alloc(Bl * dc.c_cond);
         p->named["emb"] = p->emb;
+    }
+    if (ig) {   // gradient temporaries of avc_backward_ragged (one branch, one stream, no weight gradient: two ping-pong pairs suffice)
+        EncNet& e = p->spk;
+        const long C = e.c.c_h, sumT = p->rl_spk[0].off[B];
+        e.dcat = p->alloc((long)e.CC * sumT);
+        e.dx = p->alloc((long)e.c.c_in * sumT);
+        p->gA2 = p->alloc(C * sumT);    // G_l: d(loss)/d(out_l), the residual path's gradient
+        p->gC2 = p->alloc(C * sumT);
+        p->gA = p->alloc(C * sumT);     // masked gradients entering conv2 / conv1 of a block
+        p->gB = p->alloc(C * sumT);
+        p->demb = p->alloc(Bl * dc.c_cond);
+        p->dhA = p->alloc(C * Bl);
+        p->dz = p->alloc(C * Bl);       // the dense stack's d(pre-activation) rows: written by its backward kernel, read by nobody (no weight gradient)
+        p->named["d_x_cond"] = e.dx;
+        // the saved activations the backward pass masks by (tests read the ReLU branch the engine took from them)
+        p->named["spk_cat"] = e.cat;
+        p->named["spk_h0"] = e.h0;
+        for (int l = 0; l < e.n; ++l) {
+            p->named["spk_a1_" + std::to_string(l)] = e.a1[l];
+            p->named["spk_a2_" + std::to_string(l)] = e.a2[l];
+        }
+        for (int l = 0; l < e.nd; ++l) {
+            p->named["spk_d1_" + std::to_string(l)] = e.d1[l];
+            p->named["spk_d2_" + std::to_string(l)] = e.d2[l];
+        }
     }
     if (do_enc) {   // (... and the decoder: ragged plans run it whenever the content encoder runs)
         alloc_enc(p->enc, p->rl_enc, false);
@@ -2428,4 +2468,109 @@ extern "C" int avc_forward_ragged_emb(const avc_plan* p, const float* params, co
     if (seb < 0 || sec < 0 || (p->B - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
         return fail(-1, "avc_forward_ragged_emb: emb strides must be non-negative and span less than 2^31 elements");
     return rag_forward_impl(p, params, x, nullptr, emb, seb, sec, ws, (hipStream_t)stream);
+}
+
+// The backward pass of a ragged speaker plan with AVC_PLAN_INPUT_GRADS: d(loss)/d(x_cond) from d(loss)/d(emb), parameters frozen.
+// One branch on the caller's stream, the uniform speaker branch of avc_backward_impl minus every weight gradient:
+//   d_emb -> [c_out][B] -> dense-stack backward -> d(pooled) -> pooling adjoint over each row's own length -> per block the two
+//   input-gradient launches (ragged instances of conv_gemm_kernel; the pool adjoint of the residual path rides in the second one's
+//   epilogue) -> in_conv input gradient (d(cat), masked by the bank's activations) -> the nb + 1 terms of d(x_cond), summed through the
+//   residual join of consecutive launches into ws["d_x_cond"] in x_cond's own [sum T][M] layout.
+static int rag_backward_impl(const avc_plan* p, const float* d_emb, long seb, long sec, float* ws, hipStream_t s) {
+    const int B = p->B;
+    const EncNet& e = p->spk;
+    const float SL = e.slope;
+    const std::vector<avc_plan::RagLevel>& lv = p->rl_spk;
+    const int C = e.c.c_h, M = e.c.c_in;
+    const int* tab = (const int*)(ws + p->rag_tab);
+    RUN(avc_launch_transpose_strided(ws + p->demb, d_emb, seb, sec, B, e.c.c_out, s));
+    float* dhA = ws + p->dhA;
+    {
+        DenseArgs da;
+        memset(&da, 0, sizeof(da));
+        da.nlayers = 2 * e.nd + 1;
+        da.B = B; da.C = C; da.slope = SL;
+        da.in = ws + p->demb;
+        da.dpooled = dhA;
+        for (int l = 0; l < da.nlayers; ++l) {
+            const bool last = (l == da.nlayers - 1);
+            const LayerP& L = p->layers[last ? e.outl : ((l & 1) ? e.dn2[l / 2] : e.dn1[l / 2])];
+            DenseLayer& D = da.layer[l];
+            D.wp = ws + L.wpd;
+            D.Cin = L.Cin; D.Cout = L.Cout; D.Kp = L.nchunk_d * L.CKd; D.Mp = L.Mp_d;
+            if (!last) {
+                D.act = ws + ((l & 1) ? e.d2[l / 2] : e.d1[l / 2]);
+                D.dz = ws + p->dz;
+            }
+            da.Kmax = D.Kp > da.Kmax ? D.Kp : da.Kmax;
+            da.Wmax = D.Kp * D.Mp > da.Wmax ? D.Kp * D.Mp : da.Wmax;
+        }
+        RUN(avc_launch_dense(da, 1, s));
+    }
+    float* gA = ws + p->gA2;
+    float* gC = ws + p->gC2;
+    float* dyA = ws + p->gA;
+    float* dyB = ws + p->gB;
+    // An input-gradient launch on packed rows: dy of level `sl` -> dx of level `ol` (tiles run over `ol`)
+    // (every launch below asks for the 64 x 64 tile: a ragged tile is one sample's 64 frames, the mirrored instances exist on that tile only)
+    auto dgrad = [&](const LayerP& L, const float* dy, const avc_plan::RagLevel& sl, int cx, float* dx, const avc_plan::RagLevel& ol, int cout) {
+        ConvArgs a = mk_dgrad(SL, L, ws, dy, 0, -1, 1, 1, 1, 0, 64, dx, 0, 0, 1);
+        set_rag(a, tab, sl, cx, ol, ol, cout);
+        return a;
+    };
+    RUN(avc_launch_rag_timepool_bwd(dhA, ws + e.a2[e.n - 1], tab + lv[e.n].dT, tab + lv[e.n].doff, B, C, lv[e.n].off[B], gA, dyA, SL, s));
+    for (int l = e.n - 1; l >= 0; --l) {
+        const int sub = e.c.subsample[l];
+        {   // dyB = conv2^T(dyA) masked by a1
+            ConvArgs a = dgrad(p->layers[e.c2[l]], dyA, lv[l + 1], C, nullptr, lv[l], C);
+            a.g[0].out2 = dyB;
+            a.g[0].mask = ws + e.a1[l];
+            RUN(avc_launch_conv(a, s, 11, p->tun));
+        }
+        {   // G_l = conv1^T(dyB) + pool^T(G_{l+1}); dyA = G_l masked by the activation that produced out_l
+            ConvArgs a = dgrad(p->layers[e.c1[l]], dyB, lv[l], C, l > 0 ? gC : nullptr, lv[l], C);
+            set_rag_res(a, tab, gA, sub > 1 ? AVC_RES_POOLT : AVC_RES_IDENTITY, lv[l + 1], C);
+            a.g[0].out2 = dyA;
+            a.g[0].mask = (l > 0) ? ws + e.a2[l - 1] : ws + e.h0;
+            RUN(avc_launch_conv(a, s, 11, p->tun));
+        }
+        float* t = gA; gA = gC; gC = t;
+    }
+    {   // d(cat) for the bank channels, masked by the bank's activations (cat > 0)
+        ConvArgs a = dgrad(p->layers[e.in_conv], dyA, lv[0], C, nullptr, lv[0], e.CC);
+        a.g[0].out2 = ws + e.dcat;
+        a.g[0].mask = ws + e.cat;
+        RUN(avc_launch_conv(a, s, 11, p->tun));
+    }
+    // d(x_cond) = W_in[:, nb c_bank:]^T dy_in + sum_g pad_g^T(bank_g^T(dcat_g)): nb + 1 launches, each after the first adds the running sum
+    // through its residual join, in place -- a fixed order.  Stored as [T_b][M] rows: x_cond's own layout.
+    float* dx = ws + e.dx;
+    {
+        ConvArgs a = dgrad(p->layers[e.in_pass], dyA, lv[0], C, dx, lv[0], M);
+        a.oc = 1; a.ot = M;
+        RUN(avc_launch_conv(a, s, 11, p->tun));
+    }
+    for (int g = 0; g < e.nb; ++g) {
+        ConvArgs a = dgrad(p->layers[e.bank[g]], ws + e.dcat, lv[0], e.CC, dx, lv[0], M);
+        a.rag.xc0 = g * e.c.c_bank;
+        a.oc = 1; a.ot = M;
+        set_rag_res(a, tab, dx, AVC_RES_IDENTITY, lv[0], M);
+        a.rc = 1; a.rt = M;
+        RUN(avc_launch_conv(a, s, 11, p->tun));
+    }
+    return 0;
+}
+
+extern "C" int avc_backward_ragged(const avc_plan* p, const float* params, const float* x_cond, const float* d_emb, long seb, long sec, float* ws,
+                                   void* stream) {
+    if (!p || !params || !x_cond || !d_emb || !ws)
+        return fail(-1, "avc_backward_ragged: null argument (pass the plan, params, x_cond and workspace of the avc_forward_ragged this pass follows, and d_emb [B, c_cond])");
+    if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_SPEAKER_ONLY) || !(p->flags & AVC_PLAN_INPUT_GRADS))
+        return fail(-8, "avc_backward_ragged: the plan was not created by avc_plan_create_ragged_ex with AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_INPUT_GRADS");
+    if (p->compute != AVC_COMPUTE_F32)
+        return fail(-8, "avc_backward_ragged: the plan computes with bf16 operand rounding, a forward-only model; gradients need the fp32 compute dtype "
+                        "(avc_plan_set_compute_dtype(p, 0)) or a uniform plan");
+    if (seb < 0 || sec < 0 || (p->B - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
+        return fail(-1, "avc_backward_ragged: d_emb strides must be non-negative and span less than 2^31 elements");
+    return rag_backward_impl(p, d_emb, seb, sec, ws, (hipStream_t)stream);
 }

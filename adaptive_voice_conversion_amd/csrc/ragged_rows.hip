@@ -1,4 +1,4 @@
-// Row / glue kernels of the RAGGED forward pass (AE.inference over utterances of different lengths in one launch set;
+// Row / glue kernels of the RAGGED passes (forward; backward of the speaker encoder: avc_backward_ragged) (AE.inference over utterances of different lengths in one launch set;
 // reference: inference.py:54-70, model.py:387-391 -- the reference converts one utterance per call).
 //
 // Packed buffers: sample b owns a contiguous [channels][T_b] block starting at element channels * off[b] (off = prefix sums
@@ -101,6 +101,45 @@ __global__ void __launch_bounds__(AVC_THREADS) rag_timepool_fwd_kernel(const flo
     float s = 0.f;
     for (int t = 0; t < Tb; ++t) s += p[t];
     out[(long)c * B + b] = s / (float)Tb;
+}
+
+// backward of the pooling + activation mask of the last block, the ragged twin of timepool_bwd_kernel (rowops.hip): every frame of
+// sample b's row c gets G = dP[c][b] / T_b; dy = G masked by the block's saved activation.  Packed [C][T_b] blocks.
+__global__ void __launch_bounds__(AVC_THREADS)
+rag_timepool_bwd_kernel(const float* dP, const float* amask, const int* T, const int* off, int B, int C, int sumT, float* G, float* dy, float slope) {
+    const long n = (long)C * sumT;
+    for (long e = (long)blockIdx.x * AVC_THREADS + threadIdx.x; e < n; e += (long)gridDim.x * AVC_THREADS) {
+        const int f = (int)(e / C);   // a frame index inside sample b's block (the block starts at element C * off[b])
+        const int b = rag_find(off, B, f);
+        const int Tb = T[b];
+        const int c = (int)((e - (long)C * off[b]) / Tb);
+        const float gv = dP[(long)c * B + b] / (float)Tb;
+        if (G) G[e] = gv;
+        if (dy) dy[e] = avc_act_grad(gv, amask[e] > 0.f, slope);
+    }
+}
+
+// dst[c][r] = src[r * sr + c * sc]: the caller's strided d(emb) [B, c_cond] -> the dense stack's channel-major operand
+__global__ void __launch_bounds__(AVC_THREADS) transpose_strided_kernel(float* dst, const float* src, long sr, long sc, int R, int C) {
+    const int e = blockIdx.x * AVC_THREADS + threadIdx.x;
+    if (e >= R * C) return;
+    const int c = e / R, r = e - c * R;
+    dst[e] = src[(long)r * sr + (long)c * sc];
+}
+
+int avc_launch_rag_timepool_bwd(const float* dP, const float* amask, const int* T, const int* off, int B, int C, int sumT, float* G, float* dy,
+                                float slope, hipStream_t s) {
+    const long n = (long)C * sumT;
+    long blocks = (n + AVC_THREADS - 1) / AVC_THREADS;
+    if (blocks > 2048) blocks = 2048;
+    ProfScope ps(AVC_K_MISC, 0.0, 0.0, s);
+    hipLaunchKernelGGL(rag_timepool_bwd_kernel, dim3((int)blocks), dim3(AVC_THREADS), 0, s, dP, amask, T, off, B, C, sumT, G, dy, slope);
+    return (int)hipGetLastError();
+}
+int avc_launch_transpose_strided(float* dst, const float* src, long sr, long sc, int R, int C, hipStream_t s) {
+    ProfScope ps(AVC_K_MISC, 0.0, 0.0, s);
+    hipLaunchKernelGGL(transpose_strided_kernel, dim3(avc_cdiv(R * C, AVC_THREADS)), dim3(AVC_THREADS), 0, s, dst, src, sr, sc, R, C);
+    return (int)hipGetLastError();
 }
 
 int avc_launch_rag_in_fwd(const RagINArgs& a, hipStream_t s) {

@@ -305,7 +305,8 @@ class Plan:
 
 
 class RaggedPlan:
-    """Launch plan of ONE forward-only pass over B utterances of DIFFERENT lengths (avc_plan_create_ragged_ex).  Nothing is padded.
+    """Launch plan of ONE pass over B utterances of DIFFERENT lengths (avc_plan_create_ragged_ex).  Nothing is padded.  Forward only,
+    except a "speaker" plan created with ``input_grads=True`` (below).
 
     mode "pairs" (default): B (source, target) pairs through all three networks, the batched form of
     ``Inferencer.inference_one_utterance`` (inference.py:54-70); result b equals ``AE.inference(x_b, x_cond_b)`` (model.py:387-391).
@@ -314,16 +315,22 @@ class RaggedPlan:
     mode "emb": content encoder + decoder over B sources of lengths ``T`` (``T_cond`` is ignored), the speaker embeddings come from the
     caller: ``forward_emb(params, x, emb, ws)``; result b equals ``decoder(content_encoder(x_b)[0], emb_b)``.
     The part plans pack only their networks' weights and their workspaces are smaller; in fp32 a branch computes bit for bit what it
-    computes in the "pairs" plan over the same lengths."""
+    computes in the "pairs" plan over the same lengths.
+
+    ``mode="speaker", input_grads=True`` (AVC_PLAN_INPUT_GRADS): the plan also has a backward pass with respect to its input, parameters
+    frozen, fp32 only: after ``forward(params, None, x_cond, ws)``, ``backward(params, x_cond, d_emb, ws)`` leaves d(loss)/d(x_cond) in
+    ``d_x_cond(ws)``, [sum T_cond, M] like x_cond.  Its forward is bit-identical to the plan without the flag; its workspace is larger
+    (input-gradient weight images, gradient temporaries)."""
 
     MODES = {"pairs": 0, "speaker": _lib.PLAN_SPEAKER_ONLY, "emb": _lib.PLAN_EMB_INPUT}
 
-    def __init__(self, config, T, T_cond=None, lib=None, compute_dtype="fp32", device=None, tuning=None, mode="pairs"):
+    def __init__(self, config, T, T_cond=None, lib=None, compute_dtype="fp32", device=None, tuning=None, mode="pairs", input_grads=False):
         self.lib = lib if lib is not None else _lib.load()
         self.cfg = cfg_from_dict(config)
         if mode not in self.MODES:
             raise ValueError(f"mode must be one of {sorted(self.MODES)}, got {mode!r}")
         self.mode = mode
+        self.input_grads = bool(input_grads)
         if mode == "speaker":
             if T_cond is None:
                 raise ValueError("a 'speaker' plan takes the target lengths as T_cond (T is ignored)")
@@ -350,11 +357,12 @@ class RaggedPlan:
         arr = ctypes.c_int * self.B
         dev = torch.device(device) if device is not None else None
         with (torch.cuda.device(dev) if (dev is not None and dev.type == "cuda") else contextlib.nullcontext()):
-            if mode == "pairs":
+            if mode == "pairs" and not self.input_grads:
                 rc = self.lib.avc_plan_create_ragged(ctypes.byref(self.cfg), self.B, arr(*self.T), arr(*self.T_cond), ctypes.byref(tun), ctypes.byref(h))
             else:
                 rc = self.lib.avc_plan_create_ragged_ex(ctypes.byref(self.cfg), self.B, arr(*self.T) if self.T else None,
-                                                        arr(*self.T_cond) if self.T_cond else None, self.MODES[mode], ctypes.byref(tun), ctypes.byref(h))
+                                                        arr(*self.T_cond) if self.T_cond else None,
+                                                        self.MODES[mode] | (_lib.PLAN_INPUT_GRADS if self.input_grads else 0), ctypes.byref(tun), ctypes.byref(h))
         if rc != 0:
             raise RuntimeError(self.lib.avc_last_error().decode())
         self.h = h
@@ -417,6 +425,28 @@ class RaggedPlan:
             emb = emb.contiguous()
         with _on(ws):
             self._chk(self.lib.avc_forward_ragged_emb(self.h, _ptr(params), _ptr(x), _ptr(emb), emb.stride(0), emb.stride(1), _ptr(ws), _stream(ws)))
+
+    def backward(self, params, x_cond, d_emb, ws):
+        """``mode="speaker", input_grads=True`` plans, after ``forward(params, None, x_cond, ws)`` in the same workspace: d(loss)/d(x_cond)
+        from d_emb = d(loss)/d(emb), fp32 [B, c_cond] on the workspace's device, read in place whatever its (non-negative) strides (an
+        expanded row included).  The result is ``d_x_cond(ws)``.  No parameter gradients; two calls give identical bits."""
+        if not (self.mode == "speaker" and self.input_grads):
+            raise RuntimeError("backward needs RaggedPlan(mode='speaker', input_grads=True): ragged plans are forward-only otherwise "
+                               f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
+        self._rows(x_cond, self.T_cond, "x_cond")
+        if d_emb.dim() != 2 or tuple(d_emb.shape) != (self.B, self.c_emb) or d_emb.dtype != torch.float32 or d_emb.device != ws.device:
+            raise ValueError(f"d_emb must be an fp32 [{self.B}, {self.c_emb}] tensor on {ws.device}")
+        if d_emb.stride(0) < 0 or d_emb.stride(1) < 0:
+            d_emb = d_emb.contiguous()
+        with _on(ws):
+            self._chk(self.lib.avc_backward_ragged(self.h, _ptr(params), _ptr(x_cond), _ptr(d_emb), d_emb.stride(0), d_emb.stride(1), _ptr(ws),
+                                                   _stream(ws)))
+
+    def d_x_cond(self, ws):
+        """[sum T_cond, M] view of d(loss)/d(x_cond) in the workspace (after ``backward``): rows of frames, utterance after utterance"""
+        off = self.buffer("d_x_cond")
+        n = sum(self.T_cond)
+        return ws[off:off + n * self.n_mels].view(n, self.n_mels)
 
     def emb(self, ws):
         """[B, c_cond] view of the speaker embeddings in the workspace ("pairs" and "speaker" plans)"""

@@ -316,6 +316,37 @@ class _SpeakerFunction(_PartFunction):
         return (None, dx) + _PartFunction._grads(ctx, g, "speaker")
 
 
+class _RaggedSpeakerFunction(torch.autograd.Function):
+    """``AE.get_speaker_embeddings_ragged`` with autograd with respect to its inputs (a "speaker" RaggedPlan with ``input_grads``): the
+    function's input is the packed [sum T, M] tensor ``_ragged_rows`` builds from the utterances -- torch's own autograd carries its
+    gradient back through the concatenation, device moves and views to every leaf that requires grad.  Parameters are frozen: they get
+    no gradient here (``speaker_encoder(x)`` on uniform shapes has them)."""
+
+    @staticmethod
+    def forward(ctx, ae, xc, Tc):
+        plan, entry = ae._ragged_plan("speaker_ig", (), Tc)
+        ws = entry.ws
+        if entry.busy():
+            ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=xc.device)   # private to this forward
+        token = _Token()
+        if ws is entry.ws:
+            entry.pending = weakref.ref(token)
+        plan.forward(ae._flat, None, xc, ws)
+        ctx.ae, ctx.plan, ctx.ws, ctx.token = ae, plan, ws, token
+        ctx.save_for_backward(xc)
+        return plan.emb(ws).clone()
+
+    @staticmethod
+    def backward(ctx, d_emb):
+        _PartFunction._check(ctx)
+        xc, = ctx.saved_tensors
+        if d_emb.dtype != torch.float32:
+            d_emb = d_emb.float()
+        ctx.plan.backward(ctx.ae._flat, xc, d_emb, ctx.ws)
+        ctx.token.done = True
+        return None, ctx.plan.d_x_cond(ctx.ws).clone(), None
+
+
 class _ContentFunction(_PartFunction):
     """ContentEncoder.forward (model.py:301-323) with autograd; x gets its gradient when it requires one (a plan with
     AVC_PLAN_INPUT_GRADS)."""
@@ -413,8 +444,10 @@ class AE(nn.Module):
                                   "content": 4, "decoder": 4, "speaker_train": 2, "content_train": 2, "decoder_train": 2,
                                   # ... and the plans whose backward also computes the inputs' gradients (inputs that require grad)
                                   "ig_train": 2, "speaker_ig_train": 2, "content_ig_train": 2})
-        self._ragged = {}   # (mode, lengths, device) -> (RaggedPlan, None), a few most recent; mode: "pairs" | "speaker" | "emb"
-        self._ragged_ws = None   # the one workspace they share
+        # (mode, lengths, device) -> (RaggedPlan, None | _Entry), a few most recent; mode: "pairs" | "speaker" | "emb" | "speaker_ig" (the
+        # speaker plan with input gradients; the key carries the flag, and only it has an _Entry: a workspace of its own)
+        self._ragged = {}
+        self._ragged_ws = None   # the one workspace the forward-only plans share
         self.last_ragged_compute = None
 
     # ---- flat storage ------------------------------------------------------
@@ -546,7 +579,9 @@ class AE(nn.Module):
         return self._outputs(plan, ws)[2].clone()
 
     def _ragged_plan(self, mode, T, Tc):
-        """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all three modes are kept."""
+        """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all modes are kept.  mode "speaker_ig" (the
+        speaker plan with input gradients) returns (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
+        activations between a forward and its backward and is never the pooled one."""
         from .engine import RaggedPlan
         dev = self._flat.device
         key = (mode, T, Tc, str(dev))
@@ -554,17 +589,21 @@ class AE(nn.Module):
         if hit is None:
             # compute_dtype "bf16" -> "bf16r" here: the pair-STORAGE engine takes uniform shapes only; ragged plans round the operands of
             # the matrix products to bf16 on fp32 storage (engine.RaggedPlan).  The mode that ran is reported in `last_ragged_compute`.
+            ig = mode == "speaker_ig"
             plan = RaggedPlan(self.config, T, Tc, lib=self._lib, compute_dtype="bf16r" if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")) else "fp32", device=dev,
-                              tuning=self._tuning, mode=mode)
+                              tuning=self._tuning, mode="speaker" if ig else mode, input_grads=ig)
             if [(o, n) for o, n, _ in plan.param_info] != [(o, n) for o, n, _ in self._layout]:
                 raise RuntimeError("flat parameter layout of the C plan differs from the module's")
-            hit = self._ragged[key] = (plan, None)
+            hit = self._ragged[key] = (plan, _Entry(plan, torch.zeros(plan.workspace_floats, dtype=torch.float32, device=dev)) if ig else None)
             while len(self._ragged) > 4:
                 old = self._ragged.pop(next(iter(self._ragged)))
-                old[0].close()
+                if old[1] is None:   # (a grad plan may still be needed by a pending backward -- also one that ran in a private workspace, which
+                    old[0].close()   # the entry does not track: it is never closed here, RaggedPlan.__del__ releases it once no graph holds it)
         else:
             self._ragged[key] = self._ragged.pop(key)   # most recently used last
         plan = hit[0]
+        if hit[1] is not None:
+            return plan, hit[1]
         # ONE pooled workspace for all ragged plans (real traffic almost never repeats a tuple of lengths: a fresh multi-hundred-MB
         # torch.zeros per call was most of the cold-path cost): every region a forward pass reads it has written before, in that pass
         ws = self._ragged_ws
@@ -626,8 +665,24 @@ class AE(nn.Module):
     def get_speaker_embeddings_ragged(self, x_conds):
         """``get_speaker_embeddings`` (model.py:393-395) over utterances of DIFFERENT lengths in ONE launch set: x_conds is a list of
         [T'_b, M] tensors (frames as rows, the layout ``inference_ragged`` takes); returns [B, c_emb], row b ==
-        get_speaker_embeddings(x_cond_b).  Only the speaker encoder runs (a "speaker" RaggedPlan).  Forward only."""
+        get_speaker_embeddings(x_cond_b).  Only the speaker encoder runs (a "speaker" RaggedPlan).
+
+        Differentiable with respect to its inputs: with grad enabled and at least one utterance that requires grad, the result carries a
+        ``grad_fn`` and a backward gives every such utterance a ``.grad`` of its own shape [T'_b, M] (transposed / strided views and
+        utterances on another device included; utterances that do not require grad get none).  The backward pass of all utterances is
+        ONE ragged launch set in fp32 (``RaggedPlan(mode="speaker", input_grads=True)``); the parameters are frozen on this path
+        (their gradients: ``speaker_encoder(x)`` on uniform shapes).  Grad plans have a workspace of their OWN, apart from the pooled
+        workspace of the forward-only ragged calls: no other ragged call can overwrite the saved activations between this forward and
+        its backward, and a second grad forward of the same lengths before that backward gets a private workspace.  Under
+        ``compute_dtype: bf16`` the grad path raises (ragged plans then round operands to bf16, a forward-only model): use the uniform
+        ``get_speaker_embeddings(x_b)``.  Without grad the call is the forward-only one, bit for bit."""
         Tc, xc = self._ragged_rows(x_conds, "x_conds")
+        if torch.is_grad_enabled() and xc.requires_grad:
+            if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")):
+                raise RuntimeError("get_speaker_embeddings_ragged: input gradients through the ragged path are fp32 only, and compute_dtype is "
+                                   f"{self.compute_dtype!r} (ragged plans then run 'bf16r', a forward-only rounding model).  Use the uniform path "
+                                   "get_speaker_embeddings(x_b) / speaker_encoder(x_b) per utterance, or detach the inputs")
+            return _RaggedSpeakerFunction.apply(self, xc, Tc)
         plan, ws = self._ragged_plan("speaker", (), Tc)
         plan.forward(self._flat, None, xc, ws)
         return plan.emb(ws).clone()

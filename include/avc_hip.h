@@ -291,6 +291,25 @@ int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const int* T, con
                               avc_plan** out);
 int avc_forward_ragged_emb(const avc_plan* p, const float* params, const float* x, const float* emb, long seb, long sec, float* ws,
                            void* stream);
+/* INPUT GRADIENTS THROUGH RAGGED ENROLMENT: avc_plan_create_ragged_ex(AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_INPUT_GRADS).  The flag is
+ * refused with AVC_PLAN_EMB_INPUT and on a whole ragged plan (flags without a part flag): only the ragged SPEAKER ENCODER has a backward
+ * pass.  Without the flag a speaker-only plan is what it was (pack table, workspace, launches).  With it the plan also packs the
+ * input-gradient weight images (transposed, tap-flipped) of the speaker encoder's convs, of its conv bank, of the in_conv's M
+ * pass-through rows and of the dense stack, and allocates the gradient temporaries and ws["d_x_cond"]; its forward pass is bit-identical
+ * to the unflagged plan's.
+ *   avc_backward_ragged follows an avc_forward_ragged on the SAME plan, params, x_cond and workspace (the forward leaves the activations,
+ * the weight images and the level tables there).  d_emb: d(loss)/d(emb) [B, c_cond] fp32 on the device, read in place with non-negative
+ * element strides (seb, sec) that span less than 2^31 elements, as avc_forward_ragged_emb reads emb; seb = 0 (an expanded row) is legal.
+ * params and x_cond must not be NULL but are RESERVED: the pass reads the weight images and activations the forward left in the
+ * workspace, not the parameter buffer or the input (pass what the forward got).  Result: ws["d_x_cond"] =
+ * d(loss)/d(x_cond) in x_cond's own layout, [sum T_cond][M] fp32 (utterance b = rows off[b] .. off[b] + T_cond[b]).  fp32 only (a plan
+ * whose compute dtype was set to bf16 is refused with -8: `bf16r` is a forward-only rounding model).  Parameters are frozen: no
+ * parameter gradient is computed, no weight-gradient launch is made.  No atomics and a fixed summation order (the nb + 1 terms of
+ * d(x_cond) are summed through the residual join of consecutive launches): two passes give identical bits.  Every kernel goes to the
+ * caller's stream; the call only enqueues (no allocation, no copy from the host, no synchronisation).  Refused with -8 on any plan
+ * that was not created with both flags. */
+int avc_backward_ragged(const avc_plan* p, const float* params, const float* x_cond, const float* d_emb, long seb, long sec, float* ws,
+                        void* stream);
 
 /* L1 + KL losses of solver.py:84-86 -> ws["losses"] = {loss_rec, loss_kl}; writes
  * d(lambda_rec*loss_rec)/d(dec) into ws["d_dec"] for avc_backward. */
