@@ -49,7 +49,8 @@ PLAN_CONTENT_ONLY, PLAN_DECODER_ONLY, PLAN_PART_GRADS = 32, 64, 128   # part pla
 PLAN_INPUT_GRADS = 256   # avc_backward also leaves d(loss)/d(x) in ws["d_x"] (and ws["d_x_cond"])
 FWD_WEIGHTS_PACKED = 1   # avc_forward_ex: the caller packed the weight images behind its optimizer step (avc_plan_pack_weights)
 PLAN_EMB_INPUT = 512     # ragged plans: content encoder + decoder, the embeddings come from the caller (avc_forward_ragged_emb)
-ERR_PAIR_SHAPE = -12   # avc_plan_create*: the shape is outside the bf16 pair kernels (odd channel count / frames not a multiple of 4)
+PLAN_FANOUT = 1024       # reported by avc_plan_flags on the plans of avc_plan_create_ragged_fanout (sources and outputs counted apart)
+ERR_PAIR_SHAPE = -12  # avc_plan_create*: the shape is outside the bf16 pair kernels (odd channel count / frames not a multiple of 4)
 c_void_p, c_long, c_int, c_float = ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_float
 
 
@@ -90,6 +91,11 @@ def declare(lib):
         lib.avc_plan_create_ragged_ex.argtypes = [ctypes.POINTER(ModelCfg), c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int,
                                                   ctypes.POINTER(Tuning), ctypes.POINTER(c_void_p)]
         lib.avc_forward_ragged_emb.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]
+    if hasattr(lib, "avc_plan_create_ragged_fanout"):   # (likewise)
+        lib.avc_plan_create_ragged_fanout.argtypes = [ctypes.POINTER(ModelCfg), c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int), c_int,
+                                                      ctypes.POINTER(Tuning), ctypes.POINTER(c_void_p)]
+        lib.avc_plan_ragged_latents.argtypes = [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_long)]
+        lib.avc_decoder_forward_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_long, c_void_p, c_void_p]
     if hasattr(lib, "avc_backward_ragged"):   # (likewise)
         lib.avc_backward_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_void_p, c_void_p]
     lib.avc_gather_segments.argtypes = [c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]

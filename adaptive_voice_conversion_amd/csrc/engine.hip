@@ -134,6 +134,11 @@ struct avc_plan {
         long dT = -1, doff = -1, dtile = -1;   // workspace offsets (in floats == ints) of the device copies
     };
     std::vector<RagLevel> rl_spk, rl_enc, rl_dec;   // speaker / content encoder levels 0..n, decoder levels 0..n (rl_dec[0] == rl_enc[n])
+    // fan-out plans (avc_plan_create_ragged_fanout): the decoder has a sample count of its own.  rl_z: the B SOURCES' latent level (the
+    // content encoder's last level, or the caller's latent lengths); rl_map: T / off of every OUTPUT's source in rl_z (Nd entries, no
+    // tiles: off is a gather, not a prefix sum); rl_dec: the Nd outputs.  Every other ragged plan: Nd == B, both are rl_dec[0].
+    int Nd = 0;
+    RagLevel rl_z, rl_map;
     std::vector<int> rag_host;                      // host image of all tables (uploaded by avc_forward_ragged)
     long rag_tab = -1;
     avc_tuning tun;           // launch heuristics / diagnostic switches, captured at plan creation (the dry run sizes slabs and events with them)
@@ -1437,6 +1442,7 @@ extern "C" int avc_decoder_forward(const avc_plan* p, const float* params, const
                                    long seb, long sec, float* ws, int flags, void* stream) {
     if (!p || !params || !z || !emb || !ws) return fail(-1, "avc_decoder_forward: null argument");
     if (!(p->flags & AVC_PLAN_DECODER_ONLY)) return fail(-8, "avc_decoder_forward: the plan was not created with AVC_PLAN_DECODER_ONLY");
+    if (p->flags & AVC_PLAN_RAGGED) return fail(-8, "avc_decoder_forward: ragged decoder plans run through avc_decoder_forward_ragged");
     if (flags & ~AVC_FWD_WEIGHTS_PACKED) return fail(-1, "avc_decoder_forward: unknown flag");
     const DecIn din = {z, szb, szc, szt, emb, seb, sec};
     return forward_impl(p, params, nullptr, 0, 0, 0, nullptr, 0, 0, 0, nullptr, ws, (hipStream_t)stream, (flags & AVC_FWD_WEIGHTS_PACKED) != 0,
@@ -1986,6 +1992,12 @@ extern "C" int avc_decoder_backward(const avc_plan* p, const float* params, cons
 // --------------------------------------------------------------------------
 // ragged inference: utterances of different lengths in ONE launch set
 // --------------------------------------------------------------------------
+static long rag_put(avc_plan* p, const std::vector<int>& v) {   // a table into the host image, 16-byte aligned
+    long o = (long)p->rag_host.size();
+    p->rag_host.insert(p->rag_host.end(), v.begin(), v.end());
+    while (p->rag_host.size() % 4) p->rag_host.push_back(0);
+    return o;
+}
 static void rag_level(avc_plan* p, avc_plan::RagLevel& L, const std::vector<int>& T) {
     const int B = (int)T.size();
     L.T = T;
@@ -1998,16 +2010,13 @@ static void rag_level(avc_plan* p, avc_plan::RagLevel& L, const std::vector<int>
             tiles.push_back(t0);
         }
     L.ntiles = (int)tiles.size() / 2;
-    auto put = [&](const std::vector<int>& v) {
-        long o = (long)p->rag_host.size();
-        p->rag_host.insert(p->rag_host.end(), v.begin(), v.end());
-        while (p->rag_host.size() % 4) p->rag_host.push_back(0);
-        return o;
-    };
-    L.dT = put(L.T);
-    L.doff = put(L.off);
-    L.dtile = put(tiles);
+    L.dT = rag_put(p, L.T);
+    L.doff = rag_put(p, L.off);
+    L.dtile = rag_put(p, tiles);
 }
+
+static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, int flags, int N, const int* src_of,
+                           const avc_tuning* tuning, avc_plan** out);
 
 extern "C" int avc_plan_create_ragged(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, const avc_tuning* tuning, avc_plan** out) {
     return avc_plan_create_ragged_ex(cfg, B, T, T_cond, 0, tuning, out);
@@ -2025,9 +2034,40 @@ extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const 
     if ((flags & AVC_PLAN_INPUT_GRADS) && !(flags & AVC_PLAN_SPEAKER_ONLY))
         return fail(-1, "avc_plan_create_ragged_ex: unknown flag for this ragged plan: AVC_PLAN_INPUT_GRADS is supported on ragged speaker plans only, pass AVC_PLAN_SPEAKER_ONLY | "
                         "AVC_PLAN_INPUT_GRADS (the ragged content encoder and decoder have no backward pass; use uniform plans for their gradients)");
+    return rag_plan_create(cfg, B, T, T_cond, flags, 0, nullptr, tuning, out);
+}
+
+// S sources, N outputs, output j decoded from source src_of[j] with row j of the caller's embeddings.  flags: 0 = content encoder over
+// the sources + decoder over the outputs; AVC_PLAN_CONTENT_ONLY = the content encoder alone (N = 0); AVC_PLAN_DECODER_ONLY = the decoder
+// alone, T are the latent lengths.  The speaker encoder never runs.
+extern "C" int avc_plan_create_ragged_fanout(const avc_model_cfg* cfg, int S, const int* T, int N, const int* src_of, int flags,
+                                             const avc_tuning* tuning, avc_plan** out) {
+    if (flags & ~(AVC_PLAN_CONTENT_ONLY | AVC_PLAN_DECODER_ONLY))
+        return fail(-1, "avc_plan_create_ragged_fanout: unknown flag (fan-out plans take 0, AVC_PLAN_CONTENT_ONLY or AVC_PLAN_DECODER_ONLY)");
+    if ((flags & AVC_PLAN_CONTENT_ONLY) && (flags & AVC_PLAN_DECODER_ONLY))
+        return fail(-1, "avc_plan_create_ragged_fanout: AVC_PLAN_CONTENT_ONLY and AVC_PLAN_DECODER_ONLY exclude each other");
+    if (!cfg || !out || !T || S < 1) return fail(-1, "avc_plan_create_ragged_fanout: bad arguments (S >= 1 sources of T[s] frames)");
+    if (flags & AVC_PLAN_CONTENT_ONLY) {
+        if (N != 0 || src_of) return fail(-1, "avc_plan_create_ragged_fanout: a content-only plan has no outputs: N must be 0 and src_of NULL");
+    } else {
+        if (N < 1 || !src_of) return fail(-1, "avc_plan_create_ragged_fanout: N >= 1 outputs and their sources src_of[0..N) are needed");
+        for (int j = 0; j < N; ++j)
+            if (src_of[j] < 0 || src_of[j] >= S) return fail(-1, "avc_plan_create_ragged_fanout: src_of out of range (every entry must be a source index in [0, S))");
+    }
+    const int kind = (flags & AVC_PLAN_CONTENT_ONLY) ? AVC_PLAN_CONTENT_ONLY : (AVC_PLAN_EMB_INPUT | flags);
+    return rag_plan_create(cfg, S, T, nullptr, AVC_PLAN_FANOUT | kind, N, src_of, tuning, out);
+}
+
+// flags: what avc_plan_flags reports, minus INFERENCE | RAGGED.  With AVC_PLAN_FANOUT the decoder runs over N samples mapped onto the B
+// sources by src_of; without it over the B sources themselves.
+static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, int flags, int N, const int* src_of,
+                           const avc_tuning* tuning, avc_plan** out) {
     const bool ig = (flags & AVC_PLAN_INPUT_GRADS) != 0;
-    const bool do_spk = !(flags & AVC_PLAN_EMB_INPUT), do_enc = !(flags & AVC_PLAN_SPEAKER_ONLY), do_dec = do_enc;
-    if (!do_enc) T = T_cond;   // (speaker-only: T is ignored; the shared length checks below then read T_cond twice)
+    const bool fan = (flags & AVC_PLAN_FANOUT) != 0;
+    const bool do_spk = !(flags & (AVC_PLAN_EMB_INPUT | AVC_PLAN_CONTENT_ONLY)), do_enc = !(flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_DECODER_ONLY)),
+               do_dec = !(flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_CONTENT_ONLY));
+    const int Nd = do_dec ? (fan ? N : B) : 0;   // the decoder's sample count
+    if (!do_enc && !do_dec) T = T_cond;   // (speaker-only: T is ignored; the shared length checks below then read T_cond twice)
     if (!cfg || !out || !T || B < 1) return fail(-1, "avc_plan_create_ragged: bad arguments");
     if (tuning && tuning->struct_size != (int)sizeof(avc_tuning)) return fail(-1, "avc_plan_create_ragged: avc_tuning of another library version (use avc_tuning_init)");
     if (!T_cond || !do_spk) T_cond = T;
@@ -2048,6 +2088,7 @@ extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const 
     p->tun.ck32_wgs = -1;
     p->tun.conv_x3 = 0;
     p->B = B;
+    p->Nd = Nd;
     p->M = cfg->enc.c_in;
     p->T = p->Tc = 0;
     for (int b = 0; b < B; ++b) {
@@ -2098,12 +2139,26 @@ extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const 
     };
     bool bad = (do_spk && sched(p->spk, T_cond, p->rl_spk) != 0) || (do_enc && sched(p->enc, T, p->rl_enc) != 0);
     if (!bad && do_dec) {
-        std::vector<int> cur = p->rl_enc[p->enc.n].T;
+        std::vector<int> cur = do_enc ? p->rl_enc[p->enc.n].T : std::vector<int>(T, T + B);   // (decoder-only: T are the latent lengths)
+        if (fan) {   // the sources' latent level, and every output's source in it
+            if (do_enc) p->rl_z = p->rl_enc[p->enc.n];   // (the tables the heads write by: no second copy)
+            else rag_level(p, p->rl_z, cur);
+            avc_plan::RagLevel& m = p->rl_map;
+            m.T.resize(Nd);
+            m.off.resize(Nd);
+            for (int j = 0; j < Nd; ++j) {
+                m.T[j] = p->rl_z.T[src_of[j]];
+                m.off[j] = p->rl_z.off[src_of[j]];
+            }
+            m.dT = rag_put(p, m.T);
+            m.doff = rag_put(p, m.off);
+            cur = m.T;
+        }
         p->rl_dec.resize(d.n + 1);
         for (int l = 0; l <= d.n && !bad; ++l) {
             rag_level(p, p->rl_dec[l], cur);
             if (l == d.n) break;
-            for (int b = 0; b < B; ++b) {
+            for (int b = 0; b < Nd; ++b) {
                 if (dc.kernel_size / 2 >= cur[b]) bad = true;
                 cur[b] *= dc.upsample[l];
             }
@@ -2145,14 +2200,17 @@ extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const 
         }
         finish_layer(p, p->layers[p->spk.outl], ig, 0, 1, B, B, 1, false);
     }
-    if (do_enc) {
-        finish_layer(p, p->layers[p->enc.heads], false, 0, p->rl_dec[0].ntiles, 64, 64);
-        finish_layer(p, p->layers[d.in_conv], false, 0, p->rl_dec[0].ntiles, 64, 64);
+    // every layer gets the tile count of the level it runs over: the sources' for the encoder, its heads and the decoder's in_conv, the
+    // outputs' for the decoder's blocks and out_conv (the same numbers wherever sources and outputs are the same samples)
+    const avc_plan::RagLevel* lz = do_dec ? (fan ? &p->rl_z : &p->rl_dec[0]) : (do_enc ? &p->rl_enc[p->enc.n] : nullptr);
+    if (do_enc) finish_layer(p, p->layers[p->enc.heads], false, 0, p->rl_enc[p->enc.n].ntiles, 64, 64);
+    if (do_dec) {
+        finish_layer(p, p->layers[d.in_conv], false, 0, lz->ntiles, 64, 64);
         for (int l = 0; l < d.n; ++l) {
             finish_layer(p, p->layers[d.c1[l]], false, 0, p->rl_dec[l].ntiles, 64, 64);
             finish_layer(p, p->layers[d.c2[l]], false, 0, p->rl_dec[l].ntiles, 64, 64);
         }
-        finish_layer(p, p->layers[d.affine], false, 0, 1, B, B);
+        finish_layer(p, p->layers[d.affine], false, 0, 1, Nd, Nd);
         finish_layer(p, p->layers[d.out_conv], false, 0, p->rl_dec[d.n].ntiles, 64, 64);
     }
 
@@ -2216,20 +2274,22 @@ extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const 
             p->named["spk_d2_" + std::to_string(l)] = e.d2[l];
         }
     }
-    if (do_enc) {   // (... and the decoder: ragged plans run it whenever the content encoder runs)
+    if (do_enc) {
         alloc_enc(p->enc, p->rl_enc, false);
-        p->muls = p->alloc(2 * Cz * p->rl_dec[0].off[B]);
-        d.cond = p->alloc(Bl * 2 * d.n * 2 * Cd);
-        d.y0 = p->alloc(Cd * p->rl_dec[0].off[B]);
-        d.out[0] = p->alloc(Cd * p->rl_dec[0].off[B]);
-        for (int l = 0; l < d.n; ++l) {
-            d.y1[l] = p->alloc(Cd * p->rl_dec[l].off[B]);
-            d.a1[l] = p->alloc(Cd * p->rl_dec[l].off[B]);
-            d.y2[l] = p->alloc(Cd * p->rl_dec[l + 1].off[B]);
-            d.out[l + 1] = p->alloc(Cd * p->rl_dec[l + 1].off[B]);
-        }
-        p->decb = p->alloc((long)p->M * p->rl_dec[d.n].off[B]);
+        p->muls = p->alloc(2 * Cz * lz->off[B]);
         p->named["muls"] = p->muls;
+    }
+    if (do_dec) {   // the in_conv stage lives on the B sources' level, everything above on the Nd outputs' levels
+        d.cond = p->alloc((long)Nd * 2 * d.n * 2 * Cd);
+        d.y0 = p->alloc(Cd * lz->off[B]);
+        d.out[0] = p->alloc(Cd * lz->off[B]);
+        for (int l = 0; l < d.n; ++l) {
+            d.y1[l] = p->alloc(Cd * p->rl_dec[l].off[Nd]);
+            d.a1[l] = p->alloc(Cd * p->rl_dec[l].off[Nd]);
+            d.y2[l] = p->alloc(Cd * p->rl_dec[l + 1].off[Nd]);
+            d.out[l + 1] = p->alloc(Cd * p->rl_dec[l + 1].off[Nd]);
+        }
+        p->decb = p->alloc((long)p->M * p->rl_dec[d.n].off[Nd]);
         p->named["dec"] = p->decb;
         p->named["cond"] = d.cond;
     }
@@ -2242,10 +2302,27 @@ extern "C" int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const 
 extern "C" int avc_plan_ragged_out(const avc_plan* p, int* out_len, long* out_off) {
     if (!p || !(p->flags & AVC_PLAN_RAGGED) || !out_len || !out_off) return fail(-1, "avc_plan_ragged_out: not a ragged plan");
     if (p->flags & AVC_PLAN_SPEAKER_ONLY) return fail(-8, "avc_plan_ragged_out: a speaker-only ragged plan converts nothing (its result is ws[\"emb\"])");
+    if (p->flags & AVC_PLAN_CONTENT_ONLY)
+        return fail(-8, "avc_plan_ragged_out: a content-only ragged plan decodes nothing (its result is ws[\"muls\"]: avc_plan_ragged_latents)");
     const avc_plan::RagLevel& L = p->rl_dec[p->dec.n];
-    for (int b = 0; b < p->B; ++b) {
+    for (int b = 0; b < p->Nd; ++b) {
         out_len[b] = L.T[b];
         out_off[b] = p->decb + (long)p->M * L.off[b];
+    }
+    return 0;
+}
+
+// where the content codes of every SOURCE lie: its latent length and the float offset of its [2 c_out][len] block (mu rows first)
+extern "C" int avc_plan_ragged_latents(const avc_plan* p, int* len, long* off) {
+    if (!p || !(p->flags & AVC_PLAN_RAGGED) || !len || !off) return fail(-1, "avc_plan_ragged_latents: not a ragged plan");
+    if (p->flags & AVC_PLAN_SPEAKER_ONLY)
+        return fail(-8, "avc_plan_ragged_latents: a speaker-only ragged plan has no content encoder (its result is ws[\"emb\"])");
+    if (p->flags & AVC_PLAN_DECODER_ONLY)
+        return fail(-8, "avc_plan_ragged_latents: a decoder-only ragged plan has no content encoder (its latents are the caller's: avc_decoder_forward_ragged)");
+    const avc_plan::RagLevel& L = p->rl_enc[p->enc.n];
+    for (int b = 0; b < p->B; ++b) {
+        len[b] = L.T[b];
+        off[b] = p->muls + (long)2 * p->cfg.enc.c_out * L.off[b];
     }
     return 0;
 }
@@ -2277,7 +2354,7 @@ static void set_rag_res(ConvArgs& a, const int* tab, const float* res, int mode,
     a.rt = 1;
 }
 
-static int rag_in(const avc_plan* p, float slope, const int* tab, const float* y, float* out, const avc_plan::RagLevel& lv, int C, const float* cond, long csb,
+static int rag_in(int Bn, float slope, const int* tab, const float* y, float* out, const avc_plan::RagLevel& lv, int C, const float* cond, long csb,
                   int coff, const float* res, int res_mode, const avc_plan::RagLevel* rl, hipStream_t s) {
     RagINArgs a;
     memset(&a, 0, sizeof(a));
@@ -2285,7 +2362,7 @@ static int rag_in(const avc_plan* p, float slope, const int* tab, const float* y
     a.cond = cond; a.cond_sb = csb; a.cond_off = coff;
     a.res = res; a.res_mode = res ? res_mode : 0;
     if (res) { a.Tres = tab + rl->dT; a.offres = tab + rl->doff; }
-    a.B = p->B; a.C = C; a.slope = slope;
+    a.B = Bn; a.C = C; a.slope = slope;   // (samples of level lv; the residual tables rl are indexed by the same sample)
     return avc_launch_rag_in_fwd(a, s);
 }
 
@@ -2316,9 +2393,11 @@ static int rag_enc_front(const avc_plan* p, const EncNet& e, const std::vector<a
 
 // The ragged forward pass.  emb != NULL (AVC_PLAN_EMB_INPUT plans): the decoder's AdaIN affine GEMM reads the caller's embeddings in
 // place (element strides seb, sec) and the speaker encoder does not run; otherwise it reads ws["emb"], the speaker encoder's result.
-static int rag_forward_impl(const avc_plan* p, const float* params, const float* x, const float* x_cond, const float* emb, long seb, long sec, float* ws,
-                            hipStream_t s) {
-    const bool do_spk = !(p->flags & AVC_PLAN_EMB_INPUT), do_enc = !(p->flags & AVC_PLAN_SPEAKER_ONLY);
+// z != NULL (decoder-only fan-out plans): the decoder's in_conv reads the caller's latent blocks of zc channels in place of ws["muls"].
+static int rag_forward_impl(const avc_plan* p, const float* params, const float* x, const float* x_cond, const float* emb, long seb, long sec,
+                            const float* z, int zc, float* ws, hipStream_t s) {
+    const bool do_spk = !(p->flags & (AVC_PLAN_EMB_INPUT | AVC_PLAN_CONTENT_ONLY)), do_enc = !(p->flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_DECODER_ONLY)),
+               do_dec = !(p->flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_CONTENT_ONLY));
     const int B = p->B;
     // tables -> workspace (a few KB; stream-ordered in front of everything that reads them)
     RUN((int)hipMemcpyAsync(ws + p->rag_tab, p->rag_host.data(), p->rag_host.size() * sizeof(int), hipMemcpyHostToDevice, s));
@@ -2395,48 +2474,56 @@ static int rag_forward_impl(const avc_plan* p, const float* params, const float*
         {
             ConvArgs a = conv(SL, p->layers[e.in_conv], ws + e.cat, lv[0], e.CC, ws + e.h0, lv[0], lv[0], C, 0, 1);
             RUN(avc_launch_conv(a, s, 0, p->tun));
-            RUN(rag_in(p, SL, tab, ws + e.h0, ws + e.out[0], lv[0], C, nullptr, 0, 0, nullptr, 0, nullptr, s));
+            RUN(rag_in(B, SL, tab, ws + e.h0, ws + e.out[0], lv[0], C, nullptr, 0, 0, nullptr, 0, nullptr, s));
         }
         for (int l = 0; l < e.n; ++l) {
             ConvArgs a = conv(SL, p->layers[e.c1[l]], ws + e.out[l], lv[l], C, ws + e.y1[l], lv[l], lv[l], C, 0, 1);
             RUN(avc_launch_conv(a, s, 0, p->tun));
-            RUN(rag_in(p, SL, tab, ws + e.y1[l], ws + e.a1[l], lv[l], C, nullptr, 0, 0, nullptr, 0, nullptr, s));
+            RUN(rag_in(B, SL, tab, ws + e.y1[l], ws + e.a1[l], lv[l], C, nullptr, 0, 0, nullptr, 0, nullptr, s));
             ConvArgs b = conv(SL, p->layers[e.c2[l]], ws + e.a1[l], lv[l], C, ws + e.y2[l], lv[l + 1], lv[l + 1], C, 0, 1);
             RUN(avc_launch_conv(b, s, 0, p->tun));
-            RUN(rag_in(p, SL, tab, ws + e.y2[l], ws + e.out[l + 1], lv[l + 1], C, nullptr, 0, 0, ws + e.out[l],
+            RUN(rag_in(B, SL, tab, ws + e.y2[l], ws + e.out[l + 1], lv[l + 1], C, nullptr, 0, 0, ws + e.out[l],
                        e.c.subsample[l] > 1 ? AVC_RES_AVGPOOL2 : AVC_RES_IDENTITY, &lv[l], s));
         }
         ConvArgs h = conv(SL, p->layers[e.heads], ws + e.out[e.n], lv[e.n], C, ws + p->muls, lv[e.n], lv[e.n], 2 * e.c.c_out, 0, 1);
         RUN(avc_launch_conv(h, s, 0, p->tun));
     }
     join_side(p, mainS, sideS);
-    if (do_enc) {   // ---------------- decoder(mu, emb) (model.py:347-371, :387-391: no noise)
+    if (do_dec) {   // ---------------- decoder(mu, emb) (model.py:347-371, :387-391: no noise)
         const DecNet& d = p->dec;
         const float SL = d.slope;
         const std::vector<avc_plan::RagLevel>& lv = p->rl_dec;
         const int C = d.c.c_h, Cz = d.c.c_in;
         const long csb = (long)2 * d.n * 2 * C;
+        // Fan-out plans: the B sources' latent level lz carries the voice-independent in_conv stage ONCE per source; block 0 enters the
+        // Nd outputs' levels through lm, which gives every output sample the length and the block offset of ITS source (the kernels
+        // index every table by the tile's / row's sample).  Everywhere else sources and outputs are the same samples.
+        const bool fan = (p->flags & AVC_PLAN_FANOUT) != 0;
+        const avc_plan::RagLevel& lz = fan ? p->rl_z : lv[0];
+        const avc_plan::RagLevel& lm = fan ? p->rl_map : lv[0];
+        const int Nd = p->Nd;
         const float* es = emb ? emb : ws + p->emb;
         const long esb = emb ? seb : d.c.c_cond, esc = emb ? sec : 1;
         {   // all 2n AdaIN affine Linears as ONE GEMM on emb (uniform: one row per utterance; esb = 0: every utterance reads the same row)
-            ConvArgs a = mk_fwd(p, SL, p->layers[d.affine], params, ws, es, 0, esc, (int)esb, 1, B, ws + d.cond, 0, 1, (int)csb, 0);
+            ConvArgs a = mk_fwd(p, SL, p->layers[d.affine], params, ws, es, 0, esc, (int)esb, 1, Nd, ws + d.cond, 0, 1, (int)csb, 0);
             RUN(avc_launch_conv(a, s, 0, p->tun));
         }
         {   // z = mu: the first Cz channels of every sample's (mu | log_sigma) block
-            ConvArgs a = conv(SL, p->layers[d.in_conv], ws + p->muls, lv[0], 2 * Cz, ws + d.y0, lv[0], lv[0], C, 0, 1);
+            ConvArgs a = conv(SL, p->layers[d.in_conv], z ? z : ws + p->muls, lz, z ? zc : 2 * Cz, ws + d.y0, lz, lz, C, 0, 1);
             RUN(avc_launch_conv(a, s, 0, p->tun));
-            RUN(rag_in(p, SL, tab, ws + d.y0, ws + d.out[0], lv[0], C, nullptr, 0, 0, nullptr, 0, nullptr, s));
+            RUN(rag_in(B, SL, tab, ws + d.y0, ws + d.out[0], lz, C, nullptr, 0, 0, nullptr, 0, nullptr, s));
         }
         for (int l = 0; l < d.n; ++l) {
             const int up = d.c.upsample[l];
-            ConvArgs a = conv(SL, p->layers[d.c1[l]], ws + d.out[l], lv[l], C, ws + d.y1[l], lv[l], lv[l], C, 0, 1);
+            const avc_plan::RagLevel& lin = l == 0 ? lm : lv[l];   // where out[l] lies: block 0 reads the sources' blocks
+            ConvArgs a = conv(SL, p->layers[d.c1[l]], ws + d.out[l], lin, C, ws + d.y1[l], lv[l], lv[l], C, 0, 1);
             RUN(avc_launch_conv(a, s, 0, p->tun));
-            RUN(rag_in(p, SL, tab, ws + d.y1[l], ws + d.a1[l], lv[l], C, ws + d.cond, csb, (2 * l) * 2 * C, nullptr, 0, nullptr, s));
+            RUN(rag_in(Nd, SL, tab, ws + d.y1[l], ws + d.a1[l], lv[l], C, ws + d.cond, csb, (2 * l) * 2 * C, nullptr, 0, nullptr, s));
             // second conv: C * up channels, pixel-shuffled on store into the level-(l+1) buffer (model.py:359-361)
             ConvArgs b = conv(SL, p->layers[d.c2[l]], ws + d.a1[l], lv[l], C, ws + d.y2[l], lv[l], lv[l + 1], C, 0, up);
             RUN(avc_launch_conv(b, s, 0, p->tun));
-            RUN(rag_in(p, SL, tab, ws + d.y2[l], ws + d.out[l + 1], lv[l + 1], C, ws + d.cond, csb, (2 * l + 1) * 2 * C, ws + d.out[l],
-                       up > 1 ? AVC_RES_UP2 : AVC_RES_IDENTITY, &lv[l], s));
+            RUN(rag_in(Nd, SL, tab, ws + d.y2[l], ws + d.out[l + 1], lv[l + 1], C, ws + d.cond, csb, (2 * l + 1) * 2 * C, ws + d.out[l],
+                       up > 1 ? AVC_RES_UP2 : AVC_RES_IDENTITY, &lin, s));
         }
         ConvArgs o = conv(SL, p->layers[d.out_conv], ws + d.out[d.n], lv[d.n], C, ws + p->decb, lv[d.n], lv[d.n], p->M, 0, 1);
         RUN(avc_launch_conv(o, s, 0, p->tun));
@@ -2447,27 +2534,53 @@ static int rag_forward_impl(const avc_plan* p, const float* params, const float*
 extern "C" int avc_forward_ragged(const avc_plan* p, const float* params, const float* x, const float* x_cond, float* ws, void* stream) {
     if (!p || !params || !ws) return fail(-1, "avc_forward_ragged: null argument");
     if (!(p->flags & AVC_PLAN_RAGGED)) return fail(-8, "avc_forward_ragged: the plan was not created by avc_plan_create_ragged");
+    if (p->flags & AVC_PLAN_DECODER_ONLY) return fail(-8, "avc_forward_ragged: decoder-only ragged plans run through avc_decoder_forward_ragged");
     if (p->flags & AVC_PLAN_EMB_INPUT) return fail(-8, "avc_forward_ragged: AVC_PLAN_EMB_INPUT plans run through avc_forward_ragged_emb");
     if (p->flags & AVC_PLAN_SPEAKER_ONLY) {
         if (!x_cond) return fail(-1, "avc_forward_ragged: a speaker-only plan reads x_cond (x is ignored), it must not be NULL");
-        return rag_forward_impl(p, params, nullptr, x_cond, nullptr, 0, 0, ws, (hipStream_t)stream);
+        return rag_forward_impl(p, params, nullptr, x_cond, nullptr, 0, 0, nullptr, 0, ws, (hipStream_t)stream);
     }
     if (!x) return fail(-1, "avc_forward_ragged: null argument");
+    if (p->flags & AVC_PLAN_CONTENT_ONLY)   // (the content encoder alone: x_cond is ignored, the result is ws["muls"])
+        return rag_forward_impl(p, params, x, nullptr, nullptr, 0, 0, nullptr, 0, ws, (hipStream_t)stream);
     if (!x_cond) x_cond = x;
-    return rag_forward_impl(p, params, x, x_cond, nullptr, 0, 0, ws, (hipStream_t)stream);
+    return rag_forward_impl(p, params, x, x_cond, nullptr, 0, 0, nullptr, 0, ws, (hipStream_t)stream);
 }
 
 // conversion from embeddings the caller already has (an enrolled speaker, a mean, a point between two speakers)
 extern "C" int avc_forward_ragged_emb(const avc_plan* p, const float* params, const float* x, const float* emb, long seb, long sec, float* ws,
                                       void* stream) {
     if (!p || !params || !x || !ws) return fail(-1, "avc_forward_ragged_emb: null argument");
+    if ((p->flags & AVC_PLAN_RAGGED) && (p->flags & AVC_PLAN_DECODER_ONLY))
+        return fail(-8, "avc_forward_ragged_emb: decoder-only ragged plans run through avc_decoder_forward_ragged");
+    if ((p->flags & AVC_PLAN_RAGGED) && (p->flags & AVC_PLAN_CONTENT_ONLY))
+        return fail(-8, "avc_forward_ragged_emb: content-only ragged plans run through avc_forward_ragged");
     if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_EMB_INPUT))
         return fail(-8, "avc_forward_ragged_emb: the plan was not created by avc_plan_create_ragged_ex with AVC_PLAN_EMB_INPUT");
     if (!emb) return fail(-1, "avc_forward_ragged_emb: emb is NULL (the plan has no speaker encoder to compute it)");
     // (the conv kernel addresses its source with 32-bit element offsets; -1 marks a structural zero)
-    if (seb < 0 || sec < 0 || (p->B - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
+    if (seb < 0 || sec < 0 || (p->Nd - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
         return fail(-1, "avc_forward_ragged_emb: emb strides must be non-negative and span less than 2^31 elements");
-    return rag_forward_impl(p, params, x, nullptr, emb, seb, sec, ws, (hipStream_t)stream);
+    return rag_forward_impl(p, params, x, nullptr, emb, seb, sec, nullptr, 0, ws, (hipStream_t)stream);
+}
+
+// Decoder.forward over latents of different lengths (decoder-only fan-out plans): block s of z is [zc][Tz[s]] at float offset
+// zc * offz[s]; its first c_in channels are the latent (zc = 2 c_out: the (mu | log_sigma) blocks a content plan leaves in ws["muls"])
+extern "C" int avc_decoder_forward_ragged(const avc_plan* p, const float* params, const float* z, int zc, const float* emb, long seb, long sec,
+                                          float* ws, void* stream) {
+    if (!p || !params || !z || !ws) return fail(-1, "avc_decoder_forward_ragged: null argument");
+    if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_DECODER_ONLY)) {
+        if ((p->flags & AVC_PLAN_RAGGED) && (p->flags & AVC_PLAN_EMB_INPUT))
+            return fail(-8, "avc_decoder_forward_ragged: the plan has a content encoder, it runs through avc_forward_ragged_emb");
+        if (p->flags & AVC_PLAN_RAGGED) return fail(-8, "avc_decoder_forward_ragged: the plan runs through avc_forward_ragged");
+        return fail(-8, "avc_decoder_forward_ragged: not a ragged plan (uniform decoder plans run through avc_decoder_forward)");
+    }
+    if (!emb) return fail(-1, "avc_decoder_forward_ragged: emb is NULL (the plan has no speaker encoder to compute it)");
+    if (zc < p->cfg.dec.c_in)
+        return fail(-1, "avc_decoder_forward_ragged: zc is too small: a latent block has at least c_in rows (c_in: mu alone, 2 c_out: ws[\"muls\"] blocks)");
+    if (seb < 0 || sec < 0 || (p->Nd - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
+        return fail(-1, "avc_decoder_forward_ragged: emb strides must be non-negative and span less than 2^31 elements");
+    return rag_forward_impl(p, params, nullptr, nullptr, emb, seb, sec, z, zc, ws, (hipStream_t)stream);
 }
 
 // The backward pass of a ragged speaker plan with AVC_PLAN_INPUT_GRADS: d(loss)/d(x_cond) from d(loss)/d(emb), parameters frozen.

@@ -320,18 +320,41 @@ class RaggedPlan:
     ``mode="speaker", input_grads=True`` (AVC_PLAN_INPUT_GRADS): the plan also has a backward pass with respect to its input, parameters
     frozen, fp32 only: after ``forward(params, None, x_cond, ws)``, ``backward(params, x_cond, d_emb, ws)`` leaves d(loss)/d(x_cond) in
     ``d_x_cond(ws)``, [sum T_cond, M] like x_cond.  Its forward is bit-identical to the plan without the flag; its workspace is larger
-    (input-gradient weight images, gradient temporaries)."""
+    (input-gradient weight images, gradient temporaries).
+
+    FAN-OUT (avc_plan_create_ragged_fanout; forward only): the decoder's sample count is its own.  ``T`` are the lengths of S sources,
+    ``src_of`` maps each of N outputs to its source (any order, repeats and unused sources legal; None = the identity), ``B`` stays
+    the number of sources and ``N`` is the number of outputs (``out_len`` has N entries).
+    mode "fanout": content encoder over the S sources ONCE, decoder over the N outputs: ``forward_emb(params, x, emb, ws)`` with x
+    [sum T, M] (each source once) and emb [N, c_cond]; output j equals ``decoder(content_encoder(x_{src_of[j]})[0], emb_j)``.
+    mode "encode": the content encoder alone (``src_of`` must be None): ``forward(params, x, None, ws)``, then ``latents(ws)``.
+    mode "decode": the decoder alone from the caller's latents; ``T`` are the LATENT lengths: ``forward_latents(params, z, zc, emb, ws)``."""
 
     MODES = {"pairs": 0, "speaker": _lib.PLAN_SPEAKER_ONLY, "emb": _lib.PLAN_EMB_INPUT}
+    FAN_MODES = {"fanout": 0, "encode": _lib.PLAN_CONTENT_ONLY, "decode": _lib.PLAN_DECODER_ONLY}
 
-    def __init__(self, config, T, T_cond=None, lib=None, compute_dtype="fp32", device=None, tuning=None, mode="pairs", input_grads=False):
+    def __init__(self, config, T, T_cond=None, lib=None, compute_dtype="fp32", device=None, tuning=None, mode="pairs", input_grads=False,
+                 src_of=None):
         self.lib = lib if lib is not None else _lib.load()
         self.cfg = cfg_from_dict(config)
-        if mode not in self.MODES:
-            raise ValueError(f"mode must be one of {sorted(self.MODES)}, got {mode!r}")
+        if mode not in self.MODES and mode not in self.FAN_MODES:
+            raise ValueError(f"mode must be one of {sorted(self.MODES) + sorted(self.FAN_MODES)}, got {mode!r}")
         self.mode = mode
         self.input_grads = bool(input_grads)
-        if mode == "speaker":
+        self.src_of = None
+        if src_of is not None and mode not in ("fanout", "decode"):
+            raise ValueError(f"src_of belongs to plans of mode 'fanout' or 'decode' (this one is {mode!r})")
+        if mode in self.FAN_MODES:
+            if self.input_grads:
+                raise ValueError("fan-out plans are forward only (input_grads belongs to mode='speaker')")
+            self.T = [int(t) for t in (T if T is not None else [])]
+            self.T_cond = []
+            self.B = len(self.T)
+            if mode != "encode":
+                self.src_of = [int(j) for j in (src_of if src_of is not None else range(self.B))]
+                if not self.src_of or any(not 0 <= j < self.B for j in self.src_of):
+                    raise ValueError(f"src_of must be a non-empty list of source indices in [0, {self.B}), got {self.src_of}")
+        elif mode == "speaker":
             if T_cond is None:
                 raise ValueError("a 'speaker' plan takes the target lengths as T_cond (T is ignored)")
             self.T_cond = [int(t) for t in T_cond]
@@ -355,9 +378,14 @@ class RaggedPlan:
         h = ctypes.c_void_p()
         tun = _lib.make_tuning(self.lib, tuning)
         arr = ctypes.c_int * self.B
+        self.N = len(self.src_of) if self.src_of is not None else (0 if mode == "encode" else self.B)
         dev = torch.device(device) if device is not None else None
         with (torch.cuda.device(dev) if (dev is not None and dev.type == "cuda") else contextlib.nullcontext()):
-            if mode == "pairs" and not self.input_grads:
+            if mode in self.FAN_MODES:
+                rc = self.lib.avc_plan_create_ragged_fanout(ctypes.byref(self.cfg), self.B, arr(*self.T), self.N,
+                                                            (ctypes.c_int * self.N)(*self.src_of) if self.src_of is not None else None,
+                                                            self.FAN_MODES[mode], ctypes.byref(tun), ctypes.byref(h))
+            elif mode == "pairs" and not self.input_grads:
                 rc = self.lib.avc_plan_create_ragged(ctypes.byref(self.cfg), self.B, arr(*self.T), arr(*self.T_cond), ctypes.byref(tun), ctypes.byref(h))
             else:
                 rc = self.lib.avc_plan_create_ragged_ex(ctypes.byref(self.cfg), self.B, arr(*self.T) if self.T else None,
@@ -379,13 +407,20 @@ class RaggedPlan:
             self.lib.avc_plan_param_info(h, i, ctypes.byref(off), ctypes.byref(n), ctypes.byref(dims))
             self.param_info.append((off.value, n.value, tuple(d for d in dims if d > 0)))
         self.out_len, self.out_off = [], []
-        if mode != "speaker":
-            lens, offs = (ctypes.c_int * self.B)(), (ctypes.c_long * self.B)()
+        if mode not in ("speaker", "encode"):
+            lens, offs = (ctypes.c_int * self.N)(), (ctypes.c_long * self.N)()
             if self.lib.avc_plan_ragged_out(h, lens, offs) != 0:
                 raise RuntimeError(self.lib.avc_last_error().decode())
             self.out_len, self.out_off = list(lens), list(offs)
+        self.lat_len, self.lat_off = [], []   # per SOURCE: latent frames and the float offset of its (mu | log_sigma) block in ws["muls"]
+        if mode not in ("speaker", "decode") and hasattr(self.lib, "avc_plan_ragged_latents"):
+            lens, offs = (ctypes.c_int * self.B)(), (ctypes.c_long * self.B)()
+            if self.lib.avc_plan_ragged_latents(h, lens, offs) != 0:
+                raise RuntimeError(self.lib.avc_last_error().decode())
+            self.lat_len, self.lat_off = list(lens), list(offs)
         self.n_mels = int(self.cfg.enc.c_in)
         self.c_emb = int(self.cfg.dec.c_cond)
+        self.c_lat = int(self.cfg.dec.c_in)
 
     close = Plan.close
     __del__ = Plan.__del__
@@ -399,9 +434,15 @@ class RaggedPlan:
     def forward(self, params, x, x_cond, ws):
         """x / x_cond: the utterances back to back as rows of frames, [sum T, M] contiguous fp32 (x_cond None = x).
         A "speaker" plan reads x_cond only (pass x = None)."""
-        if self.mode == "emb":
-            raise RuntimeError("an 'emb' plan has no speaker encoder: call forward_emb(params, x, emb, ws)")
-        if self.mode == "speaker":
+        if self.mode in ("emb", "fanout"):
+            raise RuntimeError(f"an {self.mode!r} plan has no speaker encoder: call forward_emb(params, x, emb, ws)")
+        if self.mode == "decode":
+            raise RuntimeError("a 'decode' plan starts from latents: call forward_latents(params, z, zc, emb, ws)")
+        if self.mode == "encode":
+            if x_cond is not None:
+                raise ValueError("an 'encode' plan runs the content encoder alone: forward(params, x, None, ws)")
+            self._rows(x, self.T, "x")
+        elif self.mode == "speaker":
             if x_cond is None:
                 raise ValueError("a 'speaker' plan reads x_cond: forward(params, None, x_cond, ws)")
             self._rows(x_cond, self.T_cond, "x_cond")
@@ -415,16 +456,46 @@ class RaggedPlan:
 
     def forward_emb(self, params, x, emb, ws):
         """"emb" plans: x as in ``forward``; emb: fp32 [B, c_cond] on the workspace's device, read in place whatever its (non-negative)
-        strides -- an ``expand``-ed [1, c_cond] row (batch stride 0) is ONE embedding for all utterances and is never materialised."""
-        if self.mode != "emb":
-            raise RuntimeError(f"forward_emb needs a plan of mode 'emb' (this one is {self.mode!r}: call forward)")
+        strides -- an ``expand``-ed [1, c_cond] row (batch stride 0) is ONE embedding for all utterances and is never materialised.
+        "fanout" plans: x holds each source once, emb is [N, c_cond], one row per output."""
+        if self.mode not in ("emb", "fanout"):
+            raise RuntimeError(f"forward_emb needs a plan of mode 'emb' or 'fanout' (this one is {self.mode!r}: call "
+                               f"{'forward_latents' if self.mode == 'decode' else 'forward'})")
         self._rows(x, self.T, "x")
-        if emb.dim() != 2 or tuple(emb.shape) != (self.B, self.c_emb) or emb.dtype != torch.float32 or emb.device != ws.device:
-            raise ValueError(f"emb must be an fp32 [{self.B}, {self.c_emb}] tensor on {ws.device}")
-        if emb.stride(0) < 0 or emb.stride(1) < 0:
-            emb = emb.contiguous()
+        emb = self._emb(emb, ws)
         with _on(ws):
             self._chk(self.lib.avc_forward_ragged_emb(self.h, _ptr(params), _ptr(x), _ptr(emb), emb.stride(0), emb.stride(1), _ptr(ws), _stream(ws)))
+
+    def _emb(self, emb, ws):
+        if emb.dim() != 2 or tuple(emb.shape) != (self.N, self.c_emb) or emb.dtype != torch.float32 or emb.device != ws.device:
+            raise ValueError(f"emb must be an fp32 [{self.N}, {self.c_emb}] tensor on {ws.device}")
+        return emb.contiguous() if (emb.stride(0) < 0 or emb.stride(1) < 0) else emb
+
+    def forward_latents(self, params, z, zc, emb, ws):
+        """"decode" plans: z holds the S latent blocks back to back, block s = [zc][T[s]] fp32 (frames contiguous) at float offset
+        zc * sum(T[:s]); the first c_lat channels of a block are read in place.  zc = c_lat: mu-only blocks; zc = 2 c_lat: the
+        ws["muls"] region of a plan with a content encoder over the same sources, passed as it is.  emb: [N, c_cond] as in ``forward_emb``."""
+        if self.mode != "decode":
+            raise RuntimeError(f"forward_latents needs a plan of mode 'decode' (this one is {self.mode!r})")
+        zc = int(zc)
+        if zc < self.c_lat:
+            raise ValueError(f"zc must be at least {self.c_lat} ({self.c_lat}: mu-only blocks; {2 * self.c_lat}: mu | log_sigma blocks), got {zc}")
+        if z.dtype != torch.float32 or z.device != ws.device or not z.is_contiguous() or z.numel() < zc * sum(self.T):
+            raise ValueError(f"z must be a contiguous fp32 tensor of at least {zc * sum(self.T)} elements on {ws.device}")
+        emb = self._emb(emb, ws)
+        with _on(ws):
+            self._chk(self.lib.avc_decoder_forward_ragged(self.h, _ptr(params), _ptr(z), zc, _ptr(emb), emb.stride(0), emb.stride(1), _ptr(ws),
+                                                          _stream(ws)))
+
+    def latents(self, ws):
+        """(list of mu, list of log_sigma): per SOURCE [c_lat, lat_len[s]] views of the content codes in the workspace (plans that run
+        the content encoder; avc_plan_ragged_latents)"""
+        if not self.lat_len:
+            raise RuntimeError(f"a plan of mode {self.mode!r} has no content codes (or the loaded library has no avc_plan_ragged_latents)")
+        c = self.c_lat
+        mu = [ws[o:o + c * n].view(c, n) for o, n in zip(self.lat_off, self.lat_len)]
+        ls = [ws[o + c * n:o + 2 * c * n].view(c, n) for o, n in zip(self.lat_off, self.lat_len)]
+        return mu, ls
 
     def backward(self, params, x_cond, d_emb, ws):
         """``mode="speaker", input_grads=True`` plans, after ``forward(params, None, x_cond, ws)`` in the same workspace: d(loss)/d(x_cond)

@@ -142,15 +142,27 @@ class Inferencer(object):
         with torch.no_grad():
             return self.model.get_speaker_embeddings_ragged(utterances).mean(0)
 
-    def convert_batch_to_wav(self, pairs, max_streams=4, do_trim=True, n_iter=None, emb=None):
+    def convert_batch_to_wav(self, pairs, max_streams=4, do_trim=True, n_iter=None, emb=None, src_of=None):
         """`convert_batch` + the audio back end: the converted mels are denormalised (inference.py:68) and vocoded by
         `melspectrogram2wav` -- all utterances, whatever their lengths, in ONE batched Griffin-Lim launch set (dsp.MelDSP).
-        ``emb``: as in ``convert_batch`` (``pairs`` is then the list of sources).
-        Returns (list of float32 waveforms, list of converted mels) in input order."""
-        mels = [self.denormalize(m.numpy()) for m in self.convert_batch(pairs, max_streams, emb=emb)]
+        ``emb`` / ``src_of``: as in ``convert_batch`` (``pairs`` is then the list of sources).
+        Returns (list of float32 waveforms, list of converted mels) in input (with ``src_of``: output) order."""
+        mels = [self.denormalize(m.numpy()) for m in self.convert_batch(pairs, max_streams, emb=emb, src_of=src_of)]
         return self.dsp().melspectrogram2wav_batch(mels, do_trim=do_trim, n_iter=n_iter), mels   # ONE Griffin-Lim launch set, any lengths
 
-    def convert_batch(self, pairs, max_streams=4, ragged=True, emb=None):
+    def convert_grid(self, sources, voices):
+        """Every source in every voice: ``sources`` is a list of S [T, M] tensors, ``voices`` a [V, c_emb] tensor of speaker embeddings
+        (``enroll``'s results stacked).  ONE fan-out launch set (``convert_batch`` with ``src_of`` = each source V times): every source
+        is uploaded and encoded once, whatever V.  Returns ``out[s][v]``, the [T'', M] CPU tensor of source s in voice v."""
+        sources = list(sources)
+        if not torch.is_tensor(voices) or voices.dim() != 2:
+            raise ValueError(f"convert_grid: voices must be a [V, {self.model._c_emb}] tensor of speaker embeddings (one row per voice), got "
+                             f"{tuple(voices.shape) if torch.is_tensor(voices) else type(voices)}")
+        S, V = len(sources), int(voices.shape[0])
+        outs = self.convert_batch(sources, emb=voices.repeat(S, 1), src_of=[s for s in range(S) for _ in range(V)])
+        return [outs[s * V:(s + 1) * V] for s in range(S)]
+
+    def convert_batch(self, pairs, max_streams=4, ragged=True, emb=None, src_of=None):
         """pairs: list of (src [T,M], tgt [T',M]) tensors of any lengths.  Default: ONE ragged launch set over all pairs
         (``AE.inference_ragged``: per-sample lengths inside every kernel; real utterances all differ in length, so shape buckets
         would be batches of one).  ``ragged=False``: the round-2 path -- pairs with equal (T, T') share one uniform plan,
@@ -161,7 +173,12 @@ class Inferencer(object):
         ``emb`` (an enrolled voice: ``enroll``'s result, [c_emb]; or one embedding per source, [B, c_emb]): ``pairs`` is then the list
         of SOURCES ([T,M] tensors) alone, converted to that voice in one ragged launch set in which the speaker encoder does not run
         (``AE.inference_ragged(xs, emb=...)``).
-        Returns the converted mels ([T'',M] CPU tensors) in input order."""
+        ``src_of`` (with ``emb``): fan-out -- output j is source ``src_of[j]`` in the voice of row j of ``emb`` ([len(src_of), c_emb], or
+        one voice for all); every source is uploaded and encoded once however often it is named (``AE.inference_ragged(xs, emb=...,
+        src_of=...)``; ``convert_grid`` is the S x V form).
+        Returns the converted mels ([T'',M] CPU tensors) in input order (with ``src_of``: one per entry of it)."""
+        if src_of is not None and emb is None:
+            raise ValueError("convert_batch: src_of goes with emb (sources alone, converted from embeddings): enrol the voices first")
         if emb is not None:
             if not ragged:
                 raise ValueError("convert_batch(sources, emb=...) runs the ragged plan; ragged=False converts (source, target) pairs")
@@ -169,7 +186,7 @@ class Inferencer(object):
             if any(isinstance(s, (tuple, list)) for s in srcs):
                 raise ValueError("convert_batch(sources, emb=...): pass the source utterances alone ([T, M] tensors), not (source, target) pairs")
             with torch.no_grad():
-                outs = self.model.inference_ragged(srcs, emb=emb)
+                outs = self.model.inference_ragged(srcs, emb=emb) if src_of is None else self.model.inference_ragged(srcs, emb=emb, src_of=src_of)
             return [o.t().cpu() for o in outs]
         if ragged:
             with torch.no_grad():

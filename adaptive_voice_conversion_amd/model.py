@@ -444,7 +444,8 @@ class AE(nn.Module):
                                   "content": 4, "decoder": 4, "speaker_train": 2, "content_train": 2, "decoder_train": 2,
                                   # ... and the plans whose backward also computes the inputs' gradients (inputs that require grad)
                                   "ig_train": 2, "speaker_ig_train": 2, "content_ig_train": 2})
-        # (mode, lengths, device) -> (RaggedPlan, None | _Entry), a few most recent; mode: "pairs" | "speaker" | "emb" | "speaker_ig" (the
+        # (mode, lengths, device[, src_of]) -> (RaggedPlan, None | _Entry), a few most recent; mode: "pairs" | "speaker" | "emb" | "fanout" |
+        # "encode" | "decode" | "speaker_ig" (the
         # speaker plan with input gradients; the key carries the flag, and only it has an _Entry: a workspace of its own)
         self._ragged = {}
         self._ragged_ws = None   # the one workspace the forward-only plans share
@@ -578,20 +579,21 @@ class AE(nn.Module):
         plan.forward(self._flat, x, x_cond, None, ws)
         return self._outputs(plan, ws)[2].clone()
 
-    def _ragged_plan(self, mode, T, Tc):
+    def _ragged_plan(self, mode, T, Tc, src_of=None):
         """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all modes are kept.  mode "speaker_ig" (the
         speaker plan with input gradients) returns (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
-        activations between a forward and its backward and is never the pooled one."""
+        activations between a forward and its backward and is never the pooled one.  ``src_of`` (a tuple; "fanout" / "decode" plans):
+        the source of every output, part of the key."""
         from .engine import RaggedPlan
         dev = self._flat.device
-        key = (mode, T, Tc, str(dev))
+        key = (mode, T, Tc, str(dev)) if src_of is None else (mode, T, Tc, str(dev), src_of)
         hit = self._ragged.get(key)
         if hit is None:
             # compute_dtype "bf16" -> "bf16r" here: the pair-STORAGE engine takes uniform shapes only; ragged plans round the operands of
             # the matrix products to bf16 on fp32 storage (engine.RaggedPlan).  The mode that ran is reported in `last_ragged_compute`.
             ig = mode == "speaker_ig"
             plan = RaggedPlan(self.config, T, Tc, lib=self._lib, compute_dtype="bf16r" if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")) else "fp32", device=dev,
-                              tuning=self._tuning, mode="speaker" if ig else mode, input_grads=ig)
+                              tuning=self._tuning, mode="speaker" if ig else mode, input_grads=ig, src_of=src_of)
             if [(o, n) for o, n, _ in plan.param_info] != [(o, n) for o, n, _ in self._layout]:
                 raise RuntimeError("flat parameter layout of the C plan differs from the module's")
             hit = self._ragged[key] = (plan, _Entry(plan, torch.zeros(plan.workspace_floats, dtype=torch.float32, device=dev)) if ig else None)
@@ -622,7 +624,33 @@ class AE(nn.Module):
                 raise ValueError(f"{name}: every utterance must be a [T, {self._n_mels}] tensor (frames as rows), got {tuple(t.shape)}")
         return tuple(int(t.shape[0]) for t in ts), torch.cat([self._prep(t).to(dev) for t in ts]).contiguous()
 
-    def inference_ragged(self, xs, x_conds=None, emb=None):
+    def _no_grad_inputs(self, call, ts, what, instead):
+        if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts):
+            raise RuntimeError(f"{call} is forward-only: {what} requires grad and its gradient would be lost.  Use the differentiable "
+                               f"uniform path {instead} or pass detached tensors")
+
+    def _src_map(self, call, src_of, S):
+        try:
+            m = tuple(int(j) for j in src_of)
+        except (TypeError, ValueError):
+            raise ValueError(f"{call}: src_of must be a list of source indices (output j is decoded from source src_of[j])") from None
+        if not m or any(not 0 <= j < S for j in m):
+            raise ValueError(f"{call}: src_of must be a non-empty list of source indices in [0, {S}) (there are {S} sources), got {list(m)}")
+        return m
+
+    def _voices(self, call, emb, N, what):
+        C = self._c_emb
+        if not torch.is_tensor(emb):
+            raise ValueError(f"{call}: emb must be a tensor of shape [{N}, {C}] or [{C}]")
+        e = self._prep(emb.detach()).to(self._flat.device)
+        if e.dim() == 1 and e.shape[0] == C:
+            e = e[None]
+        if e.dim() != 2 or e.shape[1] != C or e.shape[0] not in (1, N):
+            raise ValueError(f"{call}: emb must be [{N}, {C}] (one row per {what}), or [{C}] / [1, {C}] (one voice for all "
+                             f"{N} outputs); got {tuple(emb.shape)}")
+        return e.expand(N, C) if e.shape[0] == 1 else e   # batch stride 0: the engine reads the one row N times
+
+    def inference_ragged(self, xs, x_conds=None, emb=None, src_of=None):
         """Batched ``inference`` over utterances of DIFFERENT lengths in ONE launch set (engine.RaggedPlan; the reference converts
         one utterance per call, inference.py:62-70).  xs / x_conds: lists of [T_b, M] / [T'_b, M] tensors (frames as rows -- what
         ``utt_make_frames`` views); returns the list of converted [M, T''_b] tensors, result b == inference(x_b, x_cond_b).
@@ -631,7 +659,26 @@ class AE(nn.Module):
         a mean over enrolment utterances, a point between two speakers) -- [B, c_emb], one row per source, or [c_emb] / [1, c_emb]: one
         voice for all sources (read with batch stride 0, never expanded in memory).  The speaker encoder then does not run at all;
         result b == decoder(content_encoder(x_b)[0], emb_b), bit-identical in fp32 to the ``x_conds`` call those embeddings came from.
-        Forward only, like the ``x_conds`` form: an ``emb`` that requires grad is refused while grad is enabled."""
+        Forward only, like the ``x_conds`` form: an ``emb`` that requires grad is refused while grad is enabled.
+
+        ``src_of`` (with ``emb`` only): FAN-OUT.  ``src_of[j]`` is the source of output j (any order, repeats and unused sources
+        legal), ``emb`` is [N, c_emb] with N = len(src_of) (or one voice for all), and N tensors come back: output j ==
+        decoder(content_encoder(xs[src_of[j]])[0], emb_j), bit-identical to ``inference_ragged([xs[src_of[j]] ...], emb=emb)`` --
+        but every source is uploaded and encoded ONCE, and the decoder's voice-independent first stage runs once per source (a
+        "fanout" RaggedPlan).  Without ``src_of`` the call is what it was (an "emb" plan)."""
+        if src_of is not None:
+            if emb is None or x_conds is not None:
+                raise ValueError("inference_ragged: src_of goes with emb (speaker embeddings, [len(src_of), c_emb] or [c_emb]) and without x_conds: "
+                                 "enrol the voices first (get_speaker_embeddings_ragged)")
+            if torch.is_tensor(emb):
+                self._no_grad_inputs("inference_ragged", [emb], "emb", "decoder(z, cond) -- ae.decoder(ae.content_encoder(x)[0], emb) --")
+            self._no_grad_inputs("inference_ragged(..., src_of=...)", list(xs), "a source", "decoder(content_encoder(x)[0], emb)")
+            T, x = self._ragged_rows(xs, "xs")
+            m = self._src_map("inference_ragged", src_of, len(T))
+            e = self._voices("inference_ragged", emb, len(m), "output: len(src_of) rows")
+            plan, ws = self._ragged_plan("fanout", T, (), m)
+            plan.forward_emb(self._flat, x, e, ws)
+            return [o.clone() for o in plan.outputs(ws)]
         if (x_conds is None) == (emb is None):
             raise ValueError("inference_ragged: pass exactly one of x_conds (a list of target utterances, [T'_b, M] each) and "
                              "emb (speaker embeddings, [B, c_emb] or [c_emb])")
@@ -660,6 +707,39 @@ class AE(nn.Module):
             e = e.expand(B, C)   # batch stride 0: the engine reads the one row B times
         plan, ws = self._ragged_plan("emb", T, ())
         plan.forward_emb(self._flat, x, e, ws)
+        return [o.clone() for o in plan.outputs(ws)]
+
+    def content_latents_ragged(self, xs):
+        """The content codes of utterances of DIFFERENT lengths in ONE launch set (an "encode" RaggedPlan: the content encoder alone):
+        xs is a list of [T_s, M] tensors; returns the list of mu [c_lat, Tz_s] (Tz_s = ceil(T_s / 8) for the stock config), mu_s ==
+        content_encoder(x_s)[0], bit-identical to what ``inference_ragged`` computes inside.  Keep them and render them later, in any
+        voice, with ``decode_ragged``.  Forward only: sources that require grad are refused while grad is enabled."""
+        self._no_grad_inputs("content_latents_ragged", list(xs), "a source", "content_encoder(x)")
+        T, x = self._ragged_rows(xs, "xs")
+        plan, ws = self._ragged_plan("encode", T, ())
+        plan.forward(self._flat, x, None, ws)
+        return [mu.clone() for mu in plan.latents(ws)[0]]
+
+    def decode_ragged(self, zs, emb, src_of=None):
+        """The decoder alone over latents of DIFFERENT lengths in ONE launch set (a "decode" RaggedPlan): zs is a list of
+        [c_lat, Tz_s] tensors (``content_latents_ragged``'s, or any other), emb is [N, c_emb] or [c_emb] / [1, c_emb], ``src_of[j]`` the
+        latent of output j (None: one output per latent, in order).  Returns N tensors [M, T''_j], output j == decoder(zs[src_of[j]],
+        emb_j); with the latents of ``content_latents_ragged(xs)`` bit-identical to ``inference_ragged(xs, emb=emb, src_of=src_of)``.
+        Forward only: latents or embeddings that require grad are refused while grad is enabled."""
+        zs = list(zs)
+        if not zs:
+            raise ValueError("decode_ragged: an empty list of latents")
+        for z in zs:
+            if not torch.is_tensor(z) or z.dim() != 2 or z.shape[0] != self._c_lat:
+                raise ValueError(f"decode_ragged: every latent must be a [{self._c_lat}, Tz] tensor, got {tuple(z.shape) if torch.is_tensor(z) else type(z)}")
+        self._no_grad_inputs("decode_ragged", zs + [emb], "a latent or emb", "decoder(z, cond)")
+        dev = self._flat.device
+        Tz = tuple(int(z.shape[1]) for z in zs)
+        m = self._src_map("decode_ragged", src_of if src_of is not None else range(len(zs)), len(zs))
+        e = self._voices("decode_ragged", emb, len(m), "output")
+        z = torch.cat([self._prep(z.detach()).to(dev).reshape(-1) for z in zs])   # block s = [c_lat][Tz_s], frames contiguous
+        plan, ws = self._ragged_plan("decode", Tz, (), m)
+        plan.forward_latents(self._flat, z, self._c_lat, e, ws)
         return [o.clone() for o in plan.outputs(ws)]
 
     def get_speaker_embeddings_ragged(self, x_conds):

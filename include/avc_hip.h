@@ -19,7 +19,7 @@
  *      (1) avc_plan_create* allocates a small DEVICE table (hipMalloc: the weight-image descriptors of avc_plan_pack_weights, a few KB)
  *          and fills it with a blocking hipMemcpy; avc_plan_destroy frees it.  Create plans outside captured / latency-critical regions.
  *      (2) the FIRST plan created on a device creates that device's three helper HIP streams (below); they live until the process ends.
- *      (3) avc_forward_ragged and avc_forward_ragged_emb upload their per-utterance length / offset / tile tables (a few KB) with
+ *      (3) avc_forward_ragged, avc_forward_ragged_emb and avc_decoder_forward_ragged upload their per-utterance length / offset / tile tables (a few KB) with
  *          hipMemcpyAsync from pageable host memory: the call may block the host until the copy is staged and is NOT graph-capture safe
  *          (the uniform entry points are).
  *  - return value: 0 = ok, < 0 = bad argument / unsupported shape,
@@ -291,6 +291,39 @@ int avc_plan_create_ragged_ex(const avc_model_cfg* cfg, int B, const int* T, con
                               avc_plan** out);
 int avc_forward_ragged_emb(const avc_plan* p, const float* params, const float* x, const float* emb, long seb, long sec, float* ws,
                            void* stream);
+/* RAGGED FAN-OUT (encode each source once, decode it in many voices).  The plans above have ONE sample count for all three networks;
+ * here the decoder has its own: S sources of T[s] frames, N outputs, output j is source src_of[j] (0 <= src_of[j] < S, any order, repeats
+ * and unused sources legal) decoded with row j of the caller's embeddings.  The speaker encoder never runs (enrol first); forward only.
+ * avc_plan_create_ragged / _ex are what they were and keep refusing the flags below.  `flags` takes three values, every other bit is
+ * refused with -1:
+ *  - 0: the content encoder runs over the S sources, the decoder over the N outputs, through avc_forward_ragged_emb(p, params, x, emb,
+ *    seb, sec, ws, stream): x is [sum_s T[s]][M], each source ONCE; emb is [N, c_cond] under the stride rules of AVC_PLAN_EMB_INPUT
+ *    (seb = 0: one voice for all outputs).  avc_plan_ragged_out reports N lengths and offsets.  The decoder's voice-independent first
+ *    stage (in_conv + InstanceNorm + activation) runs once per SOURCE; its first block reads every output's source block through a
+ *    mapped length / offset table.  Output j is bit-identical to output j of an AVC_PLAN_EMB_INPUT plan over the N expanded sources
+ *    x[src_of[j]] (a column tile is 64 frames of one sample, the chunk depth of a ragged plan does not depend on its tile counts, the
+ *    row kernels work row by row), in fp32 and with avc_plan_set_compute_dtype(1).
+ *  - AVC_PLAN_CONTENT_ONLY: the content encoder alone; N must be 0 and src_of NULL.  avc_forward_ragged(p, params, x, NULL, ws, stream)
+ *    leaves ws["muls"]; avc_plan_ragged_out is refused with -8.
+ *  - AVC_PLAN_DECODER_ONLY: the decoder alone, from the caller's latents; T[s] are then the LATENT lengths Tz[s].  It runs through
+ *    avc_decoder_forward_ragged: z holds the S latent blocks back to back, block s is [zc][Tz[s]] fp32 (frames contiguous) at float
+ *    offset zc * offz[s] (offz = prefix sums of Tz), and its first c_in channel rows are read in place.  zc = 2 c_out takes the
+ *    ws["muls"] region of a content plan over the same sources as it is (a pointer into ANOTHER workspace is fine), zc = c_in takes
+ *    mu-only blocks; zc < c_in is refused with -1.  emb, seb, sec as above.
+ * avc_plan_flags reports INFERENCE | RAGGED | EMB_INPUT for the first and the third kind, plus the part flag where there is one, plus
+ * AVC_PLAN_FANOUT on all three.  Each forward entry point refuses the wrong kind of plan with -8 and avc_last_error names the call to
+ * use.  A network that does not run gets no weight image, no pack-table row, no tables and no buffers; the reflect-pad rule (-6) is
+ * checked for the networks that run only (a decoder plan: on Tz of the sources that have an output).  avc_plan_set_compute_dtype
+ * works on all three kinds.  One branch: every kernel goes to the caller's stream, no fork, no join.
+ *   avc_plan_ragged_latents (every ragged plan with a content encoder, the plans of avc_plan_create_ragged / _ex included; -8 on
+ * speaker-only and decoder-only plans): per SOURCE s its latent length len[s] (ceil(T[s] / 8) for the stock config) and the float
+ * offset off[s] of its [2 c_out][len[s]] block in the workspace (ws["muls"]; mu rows first, then log_sigma). */
+#define AVC_PLAN_FANOUT 1024   /* set by avc_plan_create_ragged_fanout (reported by avc_plan_flags); refused by every other creator */
+int avc_plan_create_ragged_fanout(const avc_model_cfg* cfg, int S, const int* T, int N, const int* src_of, int flags,
+                                  const avc_tuning* tuning, avc_plan** out);
+int avc_plan_ragged_latents(const avc_plan* p, int* len, long* off);
+int avc_decoder_forward_ragged(const avc_plan* p, const float* params, const float* z, int zc, const float* emb, long seb, long sec,
+                               float* ws, void* stream);
 /* INPUT GRADIENTS THROUGH RAGGED ENROLMENT: avc_plan_create_ragged_ex(AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_INPUT_GRADS).  The flag is
  * refused with AVC_PLAN_EMB_INPUT and on a whole ragged plan (flags without a part flag): only the ragged SPEAKER ENCODER has a backward
  * pass.  Without the flag a speaker-only plan is what it was (pack table, workspace, launches).  With it the plan also packs the
