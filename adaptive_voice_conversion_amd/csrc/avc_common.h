@@ -241,6 +241,21 @@ struct RagINArgs {
     int res_mode;
     int B, C;
     float slope;
+    float* mean;        // per row (b * C + c): the statistics the pass normalised by, saved for rag_instnorm_bwd_kernel; null (both): not stored
+    float* rstd;
+};
+
+// ragged InstanceNorm backward (ragged_rows.hip): rows of g / y / dy in the same packed [C][T_b] blocks, statistics per row (b * C + c)
+struct RagINBwdArgs {
+    const float* g;     // d(loss)/d(post-activation value) of the row (without the residual branch of the forward join)
+    const float* y;     // pre-norm rows, as the forward read them
+    const float* mean;
+    const float* rstd;
+    float* dy;
+    const int* T;
+    const int* off;
+    int B, C;
+    float slope;
 };
 
 struct INBwdArgs {

@@ -68,6 +68,7 @@ int avc_launch_reparam_fwd_pairs(const float* muls, const float* eps, int B, int
 int avc_launch_timepool_fwd_pairs(const float* in, int B, int C, int T, float* out, hipStream_t s);
 int avc_launch_timepool_bwd_pairs(const float* dP, const float* amask, int B, int C, int T, float* G, float* dy, float slope, hipStream_t s);
 int avc_launch_rag_in_fwd(const RagINArgs& a, hipStream_t s);
+int avc_launch_rag_in_bwd(const RagINBwdArgs& a, hipStream_t s);
 int avc_launch_rag_copy_rows(const float* x, long xsc, long xst, const int* T, const int* off, int B, int M, int sumT, float* dst, int CC, int c0,
                              hipStream_t s);
 int avc_launch_rag_timepool_fwd(const float* in, const int* T, const int* off, int B, int C, float* out, hipStream_t s);

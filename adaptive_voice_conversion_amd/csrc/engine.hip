@@ -2058,6 +2058,13 @@ extern "C" int avc_plan_create_ragged_fanout(const avc_model_cfg* cfg, int S, co
     return rag_plan_create(cfg, S, T, nullptr, AVC_PLAN_FANOUT | kind, N, src_of, tuning, out);
 }
 
+// The content encoder alone over S sources WITH a backward pass with respect to its input (avc_content_backward_ragged): the content-only
+// fan-out plan plus the input-gradient weight images, the saved InstanceNorm statistics and the gradient rows.
+extern "C" int avc_plan_create_ragged_content_grads(const avc_model_cfg* cfg, int S, const int* T, const avc_tuning* tuning, avc_plan** out) {
+    if (!cfg || !out || !T || S < 1) return fail(-1, "avc_plan_create_ragged_content_grads: bad arguments (S >= 1 sources of T[s] frames)");
+    return rag_plan_create(cfg, S, T, nullptr, AVC_PLAN_FANOUT | AVC_PLAN_CONTENT_ONLY | AVC_PLAN_INPUT_GRADS, 0, nullptr, tuning, out);
+}
+
 // flags: what avc_plan_flags reports, minus INFERENCE | RAGGED.  With AVC_PLAN_FANOUT the decoder runs over N samples mapped onto the B
 // sources by src_of; without it over the B sources themselves.
 static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, int flags, int N, const int* src_of,
@@ -2175,7 +2182,8 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
     for (EncNet* e : {&p->spk, &p->enc}) {
         if (!(e == &p->spk ? do_spk : do_enc)) continue;
         const std::vector<avc_plan::RagLevel>& lv = (e == &p->spk) ? p->rl_spk : p->rl_enc;
-        // (AVC_PLAN_INPUT_GRADS -- speaker plans only -- adds the input-gradient images: transposed, tap-flipped)
+        // (AVC_PLAN_INPUT_GRADS -- a speaker plan, or the content plan of avc_plan_create_ragged_content_grads -- adds the input-gradient
+        // images: transposed, tap-flipped)
         for (int id : e->bank) finish_layer(p, p->layers[id], ig, 0, lv[0].ntiles, 64, 64, e->nb);
         finish_layer(p, p->layers[e->in_conv], ig, e->CC - e->c.c_in, lv[0].ntiles, 64, 64);
         if (ig) {   // the in_conv's input gradient for its last M input rows (x itself, model.py:90): w[0] rows [nb c_bank, CC)
@@ -2203,7 +2211,7 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
     // every layer gets the tile count of the level it runs over: the sources' for the encoder, its heads and the decoder's in_conv, the
     // outputs' for the decoder's blocks and out_conv (the same numbers wherever sources and outputs are the same samples)
     const avc_plan::RagLevel* lz = do_dec ? (fan ? &p->rl_z : &p->rl_dec[0]) : (do_enc ? &p->rl_enc[p->enc.n] : nullptr);
-    if (do_enc) finish_layer(p, p->layers[p->enc.heads], false, 0, p->rl_enc[p->enc.n].ntiles, 64, 64);
+    if (do_enc) finish_layer(p, p->layers[p->enc.heads], ig, 0, p->rl_enc[p->enc.n].ntiles, 64, 64);
     if (do_dec) {
         finish_layer(p, p->layers[d.in_conv], false, 0, lz->ntiles, 64, 64);
         for (int l = 0; l < d.n; ++l) {
@@ -2249,7 +2257,7 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
         p->emb = p->alloc(Bl * dc.c_cond);
         p->named["emb"] = p->emb;
     }
-    if (ig) {   // gradient temporaries of avc_backward_ragged (one branch, one stream, no weight gradient: two ping-pong pairs suffice)
+    if (ig && do_spk) {   // gradient temporaries of avc_backward_ragged (one branch, one stream, no weight gradient: two ping-pong pairs suffice)
         EncNet& e = p->spk;
         const long C = e.c.c_h, sumT = p->rl_spk[0].off[B];
         e.dcat = p->alloc((long)e.CC * sumT);
@@ -2278,6 +2286,32 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
         alloc_enc(p->enc, p->rl_enc, false);
         p->muls = p->alloc(2 * Cz * lz->off[B]);
         p->named["muls"] = p->muls;
+    }
+    if (ig && do_enc) {   // avc_content_backward_ragged: row statistics of every InstanceNorm, d(cat), d(x), two ping-pong pairs of gradient rows
+        EncNet& e = p->enc;
+        const long C = e.c.c_h, sumT = p->rl_enc[0].off[B];
+        e.st0 = p->alloc(2 * Bl * C);   // mean[B * C] | rstd[B * C], row b * C + c
+        for (int l = 0; l < e.n; ++l) {
+            e.st1[l] = p->alloc(2 * Bl * C);
+            e.st2[l] = p->alloc(2 * Bl * C);
+        }
+        e.dcat = p->alloc((long)e.CC * sumT);
+        e.dx = p->alloc((long)e.c.c_in * sumT);
+        p->gA2 = p->alloc(C * sumT);    // G_l: d(loss)/d(out_l), the residual path's gradient
+        p->gC2 = p->alloc(C * sumT);
+        p->gA = p->alloc(C * sumT);     // d(y): what an InstanceNorm backward leaves for the conv's input gradient
+        p->gB = p->alloc(C * sumT);     // d(a1): conv2's input gradient
+        p->named["d_x"] = e.dx;
+        // what the backward pass masks by (tests read the ReLU branch the engine took: cat > 0, saved y > saved row mean)
+        p->named["enc_cat"] = e.cat;
+        p->named["enc_y0"] = e.h0;
+        p->named["enc_st0"] = e.st0;
+        for (int l = 0; l < e.n; ++l) {
+            p->named["enc_y1_" + std::to_string(l)] = e.y1[l];
+            p->named["enc_y2_" + std::to_string(l)] = e.y2[l];
+            p->named["enc_st1_" + std::to_string(l)] = e.st1[l];
+            p->named["enc_st2_" + std::to_string(l)] = e.st2[l];
+        }
     }
     if (do_dec) {   // the in_conv stage lives on the B sources' level, everything above on the Nd outputs' levels
         d.cond = p->alloc((long)Nd * 2 * d.n * 2 * Cd);
@@ -2355,7 +2389,7 @@ static void set_rag_res(ConvArgs& a, const int* tab, const float* res, int mode,
 }
 
 static int rag_in(int Bn, float slope, const int* tab, const float* y, float* out, const avc_plan::RagLevel& lv, int C, const float* cond, long csb,
-                  int coff, const float* res, int res_mode, const avc_plan::RagLevel* rl, hipStream_t s) {
+                  int coff, const float* res, int res_mode, const avc_plan::RagLevel* rl, hipStream_t s, float* stats = nullptr) {
     RagINArgs a;
     memset(&a, 0, sizeof(a));
     a.y = y; a.out = out; a.T = tab + lv.dT; a.off = tab + lv.doff;
@@ -2363,6 +2397,7 @@ static int rag_in(int Bn, float slope, const int* tab, const float* y, float* ou
     a.res = res; a.res_mode = res ? res_mode : 0;
     if (res) { a.Tres = tab + rl->dT; a.offres = tab + rl->doff; }
     a.B = Bn; a.C = C; a.slope = slope;   // (samples of level lv; the residual tables rl are indexed by the same sample)
+    if (stats) { a.mean = stats; a.rstd = stats + (long)Bn * C; }   // (plans with a backward pass keep the row statistics)
     return avc_launch_rag_in_fwd(a, s);
 }
 
@@ -2471,19 +2506,21 @@ static int rag_forward_impl(const avc_plan* p, const float* params, const float*
         const std::vector<avc_plan::RagLevel>& lv = p->rl_enc;
         const int C = e.c.c_h;
         RUN(rag_enc_front(p, e, lv, tab, params, ws, x, s));
+        const bool keep_stats = (p->flags & AVC_PLAN_INPUT_GRADS) != 0;   // (avc_plan_create_ragged_content_grads plans: the row statistics stay)
+        auto st = [&](long off) -> float* { return keep_stats ? ws + off : nullptr; };
         {
             ConvArgs a = conv(SL, p->layers[e.in_conv], ws + e.cat, lv[0], e.CC, ws + e.h0, lv[0], lv[0], C, 0, 1);
             RUN(avc_launch_conv(a, s, 0, p->tun));
-            RUN(rag_in(B, SL, tab, ws + e.h0, ws + e.out[0], lv[0], C, nullptr, 0, 0, nullptr, 0, nullptr, s));
+            RUN(rag_in(B, SL, tab, ws + e.h0, ws + e.out[0], lv[0], C, nullptr, 0, 0, nullptr, 0, nullptr, s, st(e.st0)));
         }
         for (int l = 0; l < e.n; ++l) {
             ConvArgs a = conv(SL, p->layers[e.c1[l]], ws + e.out[l], lv[l], C, ws + e.y1[l], lv[l], lv[l], C, 0, 1);
             RUN(avc_launch_conv(a, s, 0, p->tun));
-            RUN(rag_in(B, SL, tab, ws + e.y1[l], ws + e.a1[l], lv[l], C, nullptr, 0, 0, nullptr, 0, nullptr, s));
+            RUN(rag_in(B, SL, tab, ws + e.y1[l], ws + e.a1[l], lv[l], C, nullptr, 0, 0, nullptr, 0, nullptr, s, st(e.st1[l])));
             ConvArgs b = conv(SL, p->layers[e.c2[l]], ws + e.a1[l], lv[l], C, ws + e.y2[l], lv[l + 1], lv[l + 1], C, 0, 1);
             RUN(avc_launch_conv(b, s, 0, p->tun));
             RUN(rag_in(B, SL, tab, ws + e.y2[l], ws + e.out[l + 1], lv[l + 1], C, nullptr, 0, 0, ws + e.out[l],
-                       e.c.subsample[l] > 1 ? AVC_RES_AVGPOOL2 : AVC_RES_IDENTITY, &lv[l], s));
+                       e.c.subsample[l] > 1 ? AVC_RES_AVGPOOL2 : AVC_RES_IDENTITY, &lv[l], s, st(e.st2[l])));
         }
         ConvArgs h = conv(SL, p->layers[e.heads], ws + e.out[e.n], lv[e.n], C, ws + p->muls, lv[e.n], lv[e.n], 2 * e.c.c_out, 0, 1);
         RUN(avc_launch_conv(h, s, 0, p->tun));
@@ -2686,4 +2723,90 @@ extern "C" int avc_backward_ragged(const avc_plan* p, const float* params, const
     if (seb < 0 || sec < 0 || (p->B - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
         return fail(-1, "avc_backward_ragged: d_emb strides must be non-negative and span less than 2^31 elements");
     return rag_backward_impl(p, d_emb, seb, sec, ws, (hipStream_t)stream);
+}
+
+// The backward pass of a plan of avc_plan_create_ragged_content_grads: d(loss)/d(x) from d(loss)/d(mu | log_sigma), parameters frozen.  One
+// branch on the caller's stream, the uniform content branch of avc_backward_impl minus every weight gradient:
+//   d_muls -> heads^T -> per block, last to first: IN-bwd(y2) -> conv2^T -> IN-bwd(y1) -> conv1^T with the pool / identity adjoint of the
+//   residual path in its epilogue join -> IN-bwd(y0) -> in_conv input gradient (d(cat), masked by the bank's activations) -> the nb + 1 terms
+//   of d(x), summed through the residual join of consecutive launches into ws["d_x"] in x's own [sum T][M] layout (as rag_backward_impl).
+static int rag_content_backward_impl(const avc_plan* p, const float* d_muls, float* ws, hipStream_t s) {
+    const int B = p->B;
+    const EncNet& e = p->enc;
+    const float SL = e.slope;
+    const std::vector<avc_plan::RagLevel>& lv = p->rl_enc;
+    const int C = e.c.c_h, M = e.c.c_in;
+    const int* tab = (const int*)(ws + p->rag_tab);
+    float* gA = ws + p->gA2;
+    float* gC = ws + p->gC2;
+    float* dyA = ws + p->gA;
+    float* dyB = ws + p->gB;
+    // (every launch below asks for the 64 x 64 tile: a ragged tile is one sample's 64 frames, the mirrored instances exist on that tile only)
+    auto dgrad = [&](const LayerP& L, const float* dy, const avc_plan::RagLevel& sl, int cx, float* dx, const avc_plan::RagLevel& ol, int cout) {
+        ConvArgs a = mk_dgrad(SL, L, ws, dy, 0, -1, 1, 1, 1, 0, 64, dx, 0, 0, 1);
+        set_rag(a, tab, sl, cx, ol, ol, cout);
+        return a;
+    };
+    auto in_bwd_rows = [&](const float* g, long y, long st, const avc_plan::RagLevel& l, float* dy) {
+        RagINBwdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.g = g; a.y = ws + y; a.mean = ws + st; a.rstd = ws + st + (long)B * C; a.dy = dy;
+        a.T = tab + l.dT; a.off = tab + l.doff;
+        a.B = B; a.C = C; a.slope = SL;
+        return avc_launch_rag_in_bwd(a, s);
+    };
+    {   // G_n = heads^T(d_muls): the caller's [2 c_out][Tz_s] blocks
+        ConvArgs a = dgrad(p->layers[e.heads], d_muls, lv[e.n], 2 * e.c.c_out, gA, lv[e.n], C);
+        RUN(avc_launch_conv(a, s, 11, p->tun));
+    }
+    for (int l = e.n - 1; l >= 0; --l) {
+        const int sub = e.c.subsample[l];
+        RUN(in_bwd_rows(gA, e.y2[l], e.st2[l], lv[l + 1], dyA));
+        {   // d(a1) = conv2^T(d(y2))
+            ConvArgs a = dgrad(p->layers[e.c2[l]], dyA, lv[l + 1], C, dyB, lv[l], C);
+            RUN(avc_launch_conv(a, s, 11, p->tun));
+        }
+        RUN(in_bwd_rows(dyB, e.y1[l], e.st1[l], lv[l], dyA));
+        {   // G_l = conv1^T(d(y1)) + pool^T(G_{l+1})
+            ConvArgs a = dgrad(p->layers[e.c1[l]], dyA, lv[l], C, gC, lv[l], C);
+            set_rag_res(a, tab, gA, sub > 1 ? AVC_RES_POOLT : AVC_RES_IDENTITY, lv[l + 1], C);
+            RUN(avc_launch_conv(a, s, 11, p->tun));
+        }
+        float* t = gA; gA = gC; gC = t;
+    }
+    RUN(in_bwd_rows(gA, e.h0, e.st0, lv[0], dyA));
+    {   // d(cat) for the bank channels, masked by the bank's activations (cat > 0)
+        ConvArgs a = dgrad(p->layers[e.in_conv], dyA, lv[0], C, nullptr, lv[0], e.CC);
+        a.g[0].out2 = ws + e.dcat;
+        a.g[0].mask = ws + e.cat;
+        RUN(avc_launch_conv(a, s, 11, p->tun));
+    }
+    // d(x) = W_in[:, nb c_bank:]^T dy_in + sum_g pad_g^T(bank_g^T(dcat_g)): nb + 1 launches, each after the first adds the running sum through
+    // its residual join, in place -- a fixed order.  Stored as [T_b][M] rows: x's own layout.
+    float* dx = ws + e.dx;
+    {
+        ConvArgs a = dgrad(p->layers[e.in_pass], dyA, lv[0], C, dx, lv[0], M);
+        a.oc = 1; a.ot = M;
+        RUN(avc_launch_conv(a, s, 11, p->tun));
+    }
+    for (int g = 0; g < e.nb; ++g) {
+        ConvArgs a = dgrad(p->layers[e.bank[g]], ws + e.dcat, lv[0], e.CC, dx, lv[0], M);
+        a.rag.xc0 = g * e.c.c_bank;
+        a.oc = 1; a.ot = M;
+        set_rag_res(a, tab, dx, AVC_RES_IDENTITY, lv[0], M);
+        a.rc = 1; a.rt = M;
+        RUN(avc_launch_conv(a, s, 11, p->tun));
+    }
+    return 0;
+}
+
+extern "C" int avc_content_backward_ragged(const avc_plan* p, const float* params, const float* x, const float* d_muls, float* ws, void* stream) {
+    if (!p || !params || !x || !d_muls || !ws)
+        return fail(-1, "avc_content_backward_ragged: null argument (pass the avc_plan_create_ragged_content_grads plan, params, x and workspace of the avc_forward_ragged this pass follows, and d_muls)");
+    if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_CONTENT_ONLY) || !(p->flags & AVC_PLAN_INPUT_GRADS))
+        return fail(-8, "avc_content_backward_ragged: the plan was not created by avc_plan_create_ragged_content_grads");
+    if (p->compute != AVC_COMPUTE_F32)
+        return fail(-8, "avc_content_backward_ragged: the avc_plan_create_ragged_content_grads plan computes with bf16 operand rounding, a forward-only model; "
+                        "gradients need fp32 (avc_plan_set_compute_dtype(p, 0)) or a uniform plan");
+    return rag_content_backward_impl(p, d_muls, ws, (hipStream_t)stream);
 }

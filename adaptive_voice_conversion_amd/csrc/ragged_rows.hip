@@ -1,4 +1,5 @@
-// Row / glue kernels of the RAGGED passes (forward; backward of the speaker encoder: avc_backward_ragged) (AE.inference over utterances of different lengths in one launch set;
+// Row / glue kernels of the RAGGED passes (forward; backward of the speaker encoder: avc_backward_ragged; backward of the content encoder:
+// avc_content_backward_ragged) (AE.inference over utterances of different lengths in one launch set;
 // reference: inference.py:54-70, model.py:387-391 -- the reference converts one utterance per call).
 //
 // Packed buffers: sample b owns a contiguous [channels][T_b] block starting at element channels * off[b] (off = prefix sums
@@ -42,6 +43,10 @@ __global__ void __launch_bounds__(AVC_THREADS) rag_instnorm_fwd_kernel(const Rag
         beta = cr[c];
         gamma = cr[a.C + c];
     }
+    if (a.mean && l == 0) {   // (plans with a backward pass: the statistics it normalises by, so that its ReLU decision is this pass's)
+        a.mean[row] = mean;
+        a.rstd[row] = rstd;
+    }
     float* orow = a.out + base;
     int Tres = 0;
     const float* rrow = nullptr;
@@ -62,6 +67,37 @@ __global__ void __launch_bounds__(AVC_THREADS) rag_instnorm_fwd_kernel(const Rag
             }
         }
         orow[t] = w;
+    }
+}
+
+// Backward of rag_instnorm_fwd_kernel without AdaIN (gamma = 1, beta = 0: the content encoder): one wavefront per row (b, c), two passes
+// over the row's own T_b frames -- the sums of g and g * xhat (per-lane partial sums in frame order, then the fixed butterfly of wave_sum:
+// no atomics), then dy = rstd * (g - mean_t(g) - xhat * mean_t(g * xhat)).  g = G masked by the forward's ReLU decision: xhat / preact
+// come from the SAVED statistics through in_xhat / in_preact, bit for bit the forward's (instnorm_bwd_generic_kernel of rowops.hip).
+__global__ void __launch_bounds__(AVC_THREADS) rag_instnorm_bwd_kernel(const RagINBwdArgs a) {
+    const int tid = threadIdx.x, l = tid & 63;
+    const int row = blockIdx.x * 4 + (tid >> 6);
+    if (row >= a.B * a.C) return;   // (whole wavefronts leave together: a row is one wavefront)
+    const int b = row / a.C, c = row - b * a.C;
+    const int T = a.T[b];
+    const long base = (long)a.C * a.off[b] + (long)c * T;
+    const float* yrow = a.y + base;
+    const float* grow = a.g + base;
+    const float mean = a.mean[row], rstd = a.rstd[row];
+    float s1 = 0.f, s2 = 0.f;
+    for (int t = l; t < T; t += 64) {
+        const float h = in_xhat(yrow[t], mean, rstd);
+        const float gme = avc_act_grad(grow[t], in_preact(h, 1.f, 0.f) > 0.f, a.slope);
+        s1 += gme;
+        s2 += gme * h;
+    }
+    const float invT = 1.0f / (float)T;
+    const float m1 = wave_sum(s1) * invT, m2 = wave_sum(s2) * invT;
+    float* drow = a.dy + base;
+    for (int t = l; t < T; t += 64) {
+        const float h = in_xhat(yrow[t], mean, rstd);
+        const float gme = avc_act_grad(grow[t], in_preact(h, 1.f, 0.f) > 0.f, a.slope);
+        drow[t] = rstd * (gme - m1 - h * m2);
     }
 }
 
@@ -145,6 +181,11 @@ int avc_launch_transpose_strided(float* dst, const float* src, long sr, long sc,
 int avc_launch_rag_in_fwd(const RagINArgs& a, hipStream_t s) {
     ProfScope ps(AVC_K_IN_FWD, 0.0, 0.0, s);
     hipLaunchKernelGGL(rag_instnorm_fwd_kernel, dim3(avc_cdiv(a.B * a.C, 4)), dim3(AVC_THREADS), 0, s, a);
+    return (int)hipGetLastError();
+}
+int avc_launch_rag_in_bwd(const RagINBwdArgs& a, hipStream_t s) {
+    ProfScope ps(AVC_K_IN_BWD, 0.0, 0.0, s);
+    hipLaunchKernelGGL(rag_instnorm_bwd_kernel, dim3(avc_cdiv(a.B * a.C, 4)), dim3(AVC_THREADS), 0, s, a);
     return (int)hipGetLastError();
 }
 int avc_launch_rag_copy_rows(const float* x, long xsc, long xst, const int* T, const int* off, int B, int M, int sumT, float* dst, int CC, int c0,

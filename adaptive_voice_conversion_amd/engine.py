@@ -306,7 +306,7 @@ class Plan:
 
 class RaggedPlan:
     """Launch plan of ONE pass over B utterances of DIFFERENT lengths (avc_plan_create_ragged_ex).  Nothing is padded.  Forward only,
-    except a "speaker" plan created with ``input_grads=True`` (below).
+    except a "speaker" or an "encode" plan created with ``input_grads=True`` (below).
 
     mode "pairs" (default): B (source, target) pairs through all three networks, the batched form of
     ``Inferencer.inference_one_utterance`` (inference.py:54-70); result b equals ``AE.inference(x_b, x_cond_b)`` (model.py:387-391).
@@ -321,6 +321,11 @@ class RaggedPlan:
     frozen, fp32 only: after ``forward(params, None, x_cond, ws)``, ``backward(params, x_cond, d_emb, ws)`` leaves d(loss)/d(x_cond) in
     ``d_x_cond(ws)``, [sum T_cond, M] like x_cond.  Its forward is bit-identical to the plan without the flag; its workspace is larger
     (input-gradient weight images, gradient temporaries).
+
+    ``mode="encode", input_grads=True`` (avc_plan_create_ragged_content_grads): the content encoder alone with a backward pass with
+    respect to its input, parameters frozen, fp32 only: after ``forward(params, x, None, ws)``, ``backward_content(params, x, d_muls, ws)``
+    leaves d(loss)/d(x) in ``d_x(ws)``, [sum T, M] like x.  d_muls has the layout of the (mu | log_sigma) blocks ``latents(ws)`` views.
+    Forward bit-identical to the plan without the flag; a larger workspace (weight images, row statistics, gradient rows).
 
     FAN-OUT (avc_plan_create_ragged_fanout; forward only): the decoder's sample count is its own.  ``T`` are the lengths of S sources,
     ``src_of`` maps each of N outputs to its source (any order, repeats and unused sources legal; None = the identity), ``B`` stays
@@ -345,8 +350,10 @@ class RaggedPlan:
         if src_of is not None and mode not in ("fanout", "decode"):
             raise ValueError(f"src_of belongs to plans of mode 'fanout' or 'decode' (this one is {mode!r})")
         if mode in self.FAN_MODES:
-            if self.input_grads:
+            if self.input_grads and mode != "encode":
                 raise ValueError("fan-out plans are forward only (input_grads belongs to mode='speaker')")
+            if self.input_grads and not hasattr(self.lib, "avc_plan_create_ragged_content_grads"):
+                raise RuntimeError("the loaded library has no avc_plan_create_ragged_content_grads")
             self.T = [int(t) for t in (T if T is not None else [])]
             self.T_cond = []
             self.B = len(self.T)
@@ -381,7 +388,9 @@ class RaggedPlan:
         self.N = len(self.src_of) if self.src_of is not None else (0 if mode == "encode" else self.B)
         dev = torch.device(device) if device is not None else None
         with (torch.cuda.device(dev) if (dev is not None and dev.type == "cuda") else contextlib.nullcontext()):
-            if mode in self.FAN_MODES:
+            if mode == "encode" and self.input_grads:
+                rc = self.lib.avc_plan_create_ragged_content_grads(ctypes.byref(self.cfg), self.B, arr(*self.T), ctypes.byref(tun), ctypes.byref(h))
+            elif mode in self.FAN_MODES:
                 rc = self.lib.avc_plan_create_ragged_fanout(ctypes.byref(self.cfg), self.B, arr(*self.T), self.N,
                                                             (ctypes.c_int * self.N)(*self.src_of) if self.src_of is not None else None,
                                                             self.FAN_MODES[mode], ctypes.byref(tun), ctypes.byref(h))
@@ -512,6 +521,27 @@ class RaggedPlan:
         with _on(ws):
             self._chk(self.lib.avc_backward_ragged(self.h, _ptr(params), _ptr(x_cond), _ptr(d_emb), d_emb.stride(0), d_emb.stride(1), _ptr(ws),
                                                    _stream(ws)))
+
+    def backward_content(self, params, x, d_muls, ws):
+        """``mode="encode", input_grads=True`` plans, after ``forward(params, x, None, ws)`` in the same workspace: d(loss)/d(x) from
+        d_muls = d(loss)/d(mu | log_sigma): fp32, contiguous, 2 c_lat * sum(lat_len) elements on the workspace's device, block s =
+        [2 c_lat][lat_len[s]] (mu rows, then log_sigma rows) at element 2 c_lat * sum(lat_len[:s]) -- the layout of the workspace region
+        ``latents(ws)`` views.  The result is ``d_x(ws)``.  No parameter gradients; two calls give identical bits."""
+        if not (self.mode == "encode" and self.input_grads):
+            raise RuntimeError("backward_content needs RaggedPlan(mode='encode', input_grads=True) "
+                               f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
+        self._rows(x, self.T, "x")
+        n = 2 * self.c_lat * sum(self.lat_len)
+        if d_muls.dtype != torch.float32 or d_muls.device != ws.device or not d_muls.is_contiguous() or d_muls.numel() != n:
+            raise ValueError(f"d_muls must be a contiguous fp32 tensor of {n} elements on {ws.device} (the layout of the plan's latent blocks)")
+        with _on(ws):
+            self._chk(self.lib.avc_content_backward_ragged(self.h, _ptr(params), _ptr(x), _ptr(d_muls), _ptr(ws), _stream(ws)))
+
+    def d_x(self, ws):
+        """[sum T, M] view of d(loss)/d(x) in the workspace (after ``backward_content``): rows of frames, utterance after utterance"""
+        off = self.buffer("d_x")
+        n = sum(self.T)
+        return ws[off:off + n * self.n_mels].view(n, self.n_mels)
 
     def d_x_cond(self, ws):
         """[sum T_cond, M] view of d(loss)/d(x_cond) in the workspace (after ``backward``): rows of frames, utterance after utterance"""

@@ -347,6 +347,36 @@ class _RaggedSpeakerFunction(torch.autograd.Function):
         return None, ctx.plan.d_x_cond(ctx.ws).clone(), None
 
 
+class _RaggedContentFunction(torch.autograd.Function):
+    """``AE.content_encoder_ragged`` with autograd with respect to its inputs (an "encode" RaggedPlan with ``input_grads``), modelled on
+    ``_RaggedSpeakerFunction``: the function's input is the packed [sum T, M] tensor, its output the packed latents -- block s is
+    [2 c_lat][Tz_s], mu rows then log_sigma rows, the layout of ws["muls"].  The caller's per-utterance mu / log_sigma are views of that
+    output, so torch's own autograd gathers their gradients into the packed d_muls the plan reads.  Parameters are frozen."""
+
+    @staticmethod
+    def forward(ctx, ae, x, T):
+        plan, entry = ae._ragged_plan("encode_ig", T, ())
+        ws = entry.ws
+        if entry.busy():
+            ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=x.device)   # private to this forward
+        token = _Token()
+        if ws is entry.ws:
+            entry.pending = weakref.ref(token)
+        plan.forward(ae._flat, x, None, ws)
+        ctx.ae, ctx.plan, ctx.ws, ctx.token = ae, plan, ws, token
+        ctx.save_for_backward(x)
+        o = plan.lat_off[0]
+        return ws[o:o + 2 * plan.c_lat * sum(plan.lat_len)].clone()
+
+    @staticmethod
+    def backward(ctx, d_muls):
+        _PartFunction._check(ctx)
+        x, = ctx.saved_tensors
+        ctx.plan.backward_content(ctx.ae._flat, x, d_muls.float().contiguous(), ctx.ws)
+        ctx.token.done = True
+        return None, ctx.plan.d_x(ctx.ws).clone(), None
+
+
 class _ContentFunction(_PartFunction):
     """ContentEncoder.forward (model.py:301-323) with autograd; x gets its gradient when it requires one (a plan with
     AVC_PLAN_INPUT_GRADS)."""
@@ -580,8 +610,8 @@ class AE(nn.Module):
         return self._outputs(plan, ws)[2].clone()
 
     def _ragged_plan(self, mode, T, Tc, src_of=None):
-        """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all modes are kept.  mode "speaker_ig" (the
-        speaker plan with input gradients) returns (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
+        """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all modes are kept.  modes "speaker_ig" and
+        "encode_ig" (the speaker / content plan with input gradients) return (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
         activations between a forward and its backward and is never the pooled one.  ``src_of`` (a tuple; "fanout" / "decode" plans):
         the source of every output, part of the key."""
         from .engine import RaggedPlan
@@ -591,9 +621,9 @@ class AE(nn.Module):
         if hit is None:
             # compute_dtype "bf16" -> "bf16r" here: the pair-STORAGE engine takes uniform shapes only; ragged plans round the operands of
             # the matrix products to bf16 on fp32 storage (engine.RaggedPlan).  The mode that ran is reported in `last_ragged_compute`.
-            ig = mode == "speaker_ig"
+            ig = mode in ("speaker_ig", "encode_ig")
             plan = RaggedPlan(self.config, T, Tc, lib=self._lib, compute_dtype="bf16r" if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")) else "fp32", device=dev,
-                              tuning=self._tuning, mode="speaker" if ig else mode, input_grads=ig, src_of=src_of)
+                              tuning=self._tuning, mode=mode[:-3] if ig else mode, input_grads=ig, src_of=src_of)
             if [(o, n) for o, n, _ in plan.param_info] != [(o, n) for o, n, _ in self._layout]:
                 raise RuntimeError("flat parameter layout of the C plan differs from the module's")
             hit = self._ragged[key] = (plan, _Entry(plan, torch.zeros(plan.workspace_floats, dtype=torch.float32, device=dev)) if ig else None)
@@ -719,6 +749,35 @@ class AE(nn.Module):
         plan, ws = self._ragged_plan("encode", T, ())
         plan.forward(self._flat, x, None, ws)
         return [mu.clone() for mu in plan.latents(ws)[0]]
+
+    def content_encoder_ragged(self, xs):
+        """``content_encoder`` over utterances of DIFFERENT lengths in ONE launch set: xs is a list of [T_s, M] tensors (frames as rows);
+        returns (list of mu [c_lat, Tz_s], list of log_sigma [c_lat, Tz_s]), entry s == content_encoder(x_s), bit-identical to
+        ``content_latents_ragged``.
+
+        Differentiable with respect to its inputs: with grad enabled and at least one utterance that requires grad, the results are
+        views of ONE packed tensor with a ``grad_fn``, and a backward gives every such utterance a ``.grad`` of its own shape [T_s, M]
+        (utterances that do not require grad get none).  The backward pass of all utterances is ONE ragged launch set in fp32
+        (``RaggedPlan(mode="encode", input_grads=True)``); the parameters are frozen on this path (their gradients:
+        ``content_encoder(x)`` on uniform shapes).  Grad plans have a workspace of their OWN (see ``get_speaker_embeddings_ragged``); a
+        second grad forward of the same lengths while a backward is pending gets a private workspace.  Under ``compute_dtype: bf16`` the
+        grad path raises: use the uniform ``content_encoder(x_b)``.  Without grad the call runs the pooled forward-only "encode" plan."""
+        T, x = self._ragged_rows(xs, "xs")
+        if torch.is_grad_enabled() and x.requires_grad:
+            if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")):
+                raise RuntimeError("content_encoder_ragged: input gradients through the ragged path are fp32 only, and compute_dtype is "
+                                   f"{self.compute_dtype!r} (ragged plans then run 'bf16r', a forward-only rounding model).  Use the uniform path "
+                                   "content_encoder(x_b) per utterance, or detach the inputs")
+            muls = _RaggedContentFunction.apply(self, x, T)
+            plan = self._ragged_plan("encode_ig", T, ())[0]
+            c, base = plan.c_lat, plan.lat_off[0]
+            mu = [muls[o - base:o - base + c * n].view(c, n) for o, n in zip(plan.lat_off, plan.lat_len)]
+            ls = [muls[o - base + c * n:o - base + 2 * c * n].view(c, n) for o, n in zip(plan.lat_off, plan.lat_len)]
+            return mu, ls
+        plan, ws = self._ragged_plan("encode", T, ())
+        plan.forward(self._flat, x, None, ws)
+        mu, ls = plan.latents(ws)
+        return [m.clone() for m in mu], [l.clone() for l in ls]
 
     def decode_ragged(self, zs, emb, src_of=None):
         """The decoder alone over latents of DIFFERENT lengths in ONE launch set (a "decode" RaggedPlan): zs is a list of

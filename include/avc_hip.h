@@ -325,8 +325,8 @@ int avc_plan_ragged_latents(const avc_plan* p, int* len, long* off);
 int avc_decoder_forward_ragged(const avc_plan* p, const float* params, const float* z, int zc, const float* emb, long seb, long sec,
                                float* ws, void* stream);
 /* INPUT GRADIENTS THROUGH RAGGED ENROLMENT: avc_plan_create_ragged_ex(AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_INPUT_GRADS).  The flag is
- * refused with AVC_PLAN_EMB_INPUT and on a whole ragged plan (flags without a part flag): only the ragged SPEAKER ENCODER has a backward
- * pass.  Without the flag a speaker-only plan is what it was (pack table, workspace, launches).  With it the plan also packs the
+ * refused with AVC_PLAN_EMB_INPUT and on a whole ragged plan (flags without a part flag): through this creator only the ragged SPEAKER
+ * ENCODER has a backward pass (the content encoder's: avc_plan_create_ragged_content_grads below).  Without the flag a speaker-only plan is what it was (pack table, workspace, launches).  With it the plan also packs the
  * input-gradient weight images (transposed, tap-flipped) of the speaker encoder's convs, of its conv bank, of the in_conv's M
  * pass-through rows and of the dense stack, and allocates the gradient temporaries and ws["d_x_cond"]; its forward pass is bit-identical
  * to the unflagged plan's.
@@ -343,6 +343,30 @@ int avc_decoder_forward_ragged(const avc_plan* p, const float* params, const flo
  * that was not created with both flags. */
 int avc_backward_ragged(const avc_plan* p, const float* params, const float* x_cond, const float* d_emb, long seb, long sec, float* ws,
                         void* stream);
+/* INPUT GRADIENTS THROUGH THE RAGGED CONTENT ENCODER: avc_plan_create_ragged_content_grads(cfg, S, T, tuning, out) creates the content
+ * encoder alone over S sources of T[s] frames -- the AVC_PLAN_CONTENT_ONLY plan of avc_plan_create_ragged_fanout -- with a backward pass
+ * with respect to its input.  avc_plan_flags reports what that plan reports plus AVC_PLAN_INPUT_GRADS; avc_plan_ragged_latents works; the
+ * reflect-pad rule is the forward plan's (-6).  Its forward runs through avc_forward_ragged(p, params, x, NULL, ws, stream) and launches
+ * the same kernel instances on the same operands as the plan without a backward pass: ws["muls"] is bit-identical.  On top of that plan
+ * it packs (in the plan's one pack launch) the input-gradient weight images (transposed, tap-flipped) of the blocks' convs, the heads, the
+ * in_conv, the conv bank and the in_conv's M pass-through rows, its InstanceNorm launches store the mean / rstd of every row, and the
+ * workspace holds d(cat), ws["d_x"] and two ping-pong pairs of gradient rows.  The existing creators keep refusing AVC_PLAN_INPUT_GRADS
+ * wherever they did, and avc_backward_ragged keeps refusing every plan that is not a flagged speaker plan, this one included.
+ *   avc_content_backward_ragged follows an avc_forward_ragged on the SAME plan, params, x and workspace.  d_muls: d(loss)/d(mu | log_sigma),
+ * fp32, contiguous, in the layout of ws["muls"]: block s is [2 c_out][Tz_s] at float offset 2 c_out * offz[s] (avc_plan_ragged_latents),
+ * mu rows first, then log_sigma rows.  params and x must not be NULL but are RESERVED (the pass reads the weight images, pre-norm rows and
+ * statistics the forward left in the workspace).  Result: ws["d_x"] = d(loss)/d(x) in x's own layout, [sum T][M] fp32.  Launches, in
+ * order: the heads' 1x1 input gradient; per block from last to first InstanceNorm backward of y2 (one wavefront per row at the row's own
+ * length, the ReLU decision recomputed from the SAVED statistics: the forward's, bit for bit), conv2's input gradient, InstanceNorm
+ * backward of y1, conv1's input gradient with the pool / identity adjoint of the residual path in its epilogue join; InstanceNorm backward
+ * of the in_conv's rows; the in_conv's input gradient masked by cat > 0; the nb + 1 terms of d(x) summed through the residual join of
+ * consecutive launches.  fp32 only (-8 when the plan's compute dtype is bf16), parameters frozen, no weight gradients, no atomics, a fixed
+ * summation order: two passes give identical bits.  Every kernel goes to the caller's stream; the call only enqueues.  -8 on any other
+ * plan, -1 on a null argument.  Further named buffers of such a plan (avc_plan_buffer): "enc_cat" (the concat buffer), "enc_y0",
+ * "enc_y1_<l>", "enc_y2_<l>" (the pre-norm rows, packed [c_h][T_s] blocks) and "enc_st0", "enc_st1_<l>", "enc_st2_<l>" (their statistics:
+ * mean[S * c_h] then rstd[S * c_h], row s * c_h + c). */
+int avc_plan_create_ragged_content_grads(const avc_model_cfg* cfg, int S, const int* T, const avc_tuning* tuning, avc_plan** out);
+int avc_content_backward_ragged(const avc_plan* p, const float* params, const float* x, const float* d_muls, float* ws, void* stream);
 
 /* L1 + KL losses of solver.py:84-86 -> ws["losses"] = {loss_rec, loss_kl}; writes
  * d(lambda_rec*loss_rec)/d(dec) into ws["d_dec"] for avc_backward. */
