@@ -333,6 +333,9 @@ static __device__ __forceinline__ float avc_act_grad(float g, bool positive, flo
 // x_hat and the ReLU pre-activation of the InstanceNorm family are computed by the SAME explicitly
 // rounded sequence wherever they appear (row kernels forward and backward, fused conv epilogue), so a
 // recomputed ReLU mask is bit-identical to the forward decision whatever the compiler contracts.
+// The MEAN handed in must be a rounded fp32 value that is also what gets saved: forward kernels form it as sum / T, a division.
+// The product sum * (1 / T) is contracted into the subtraction below (one fma on the unrounded product), and for T that is no power
+// of two the forward then decides on another mean than the backward reads back.
 static __device__ __forceinline__ float in_xhat(float y, float mean, float rstd) { return __fmul_rn(__fsub_rn(y, mean), rstd); }
 static __device__ __forceinline__ float in_preact(float xh, float gamma, float beta) { return __fmaf_rn(xh, gamma, beta); }
 
@@ -352,6 +355,7 @@ static __device__ __forceinline__ f32x16 avc_mfma_bf16(avc_s16x4 a, avc_s16x4 b,
 static inline short avc_bf16_bits(float f) {
     unsigned u;
     memcpy(&u, &f, 4);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (short)((u >> 16) | 0x0040u);   // NaN in, quiet NaN out, sign kept (the carry below would turn a low payload into Inf or -0)
     u += 0x7FFFu + ((u >> 16) & 1u);
     return (short)(u >> 16);
 }

@@ -238,7 +238,7 @@ static __device__ void conv_epilogue_in(const ConvArgs& a, const ConvGroup& g, c
     for (int k = 0; k < 4; ++k) s += (v[4 * k] + v[4 * k + 1]) + (v[4 * k + 2] + v[4 * k + 3]);
     for (int o = 1; o < lpr; o <<= 1) s += __shfl_xor(s, o);
     if (ops == 2) s += __shfl_xor(s, 4);
-    const float mean = s * invT;
+    const float mean = s / (float)Tn;   // see in_xhat
     float ss = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -459,7 +459,7 @@ static __device__ void conv_epilogue_in_pairs(const ConvArgs& a, const ConvGroup
 #pragma unroll
     for (int k = 0; k < 4; ++k) s += (v[4 * k] + v[4 * k + 1]) + (v[4 * k + 2] + v[4 * k + 3]);
     for (int o = 1; o < lpr; o <<= 1) s += __shfl_xor(s, o);
-    const float mean = s * invT;
+    const float mean = s / (float)Tout;   // see in_xhat
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {

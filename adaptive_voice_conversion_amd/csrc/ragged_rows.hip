@@ -30,7 +30,7 @@ __global__ void __launch_bounds__(AVC_THREADS) rag_instnorm_fwd_kernel(const Rag
     float s = 0.f;
     for (int t = l; t < T; t += 64) s += yrow[t];
     const float invT = 1.0f / (float)T;
-    const float mean = wave_sum(s) * invT;
+    const float mean = wave_sum(s) / (float)T;   // see in_xhat
     float ss = 0.f;
     for (int t = l; t < T; t += 64) {
         float d = yrow[t] - mean;

@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(AVC_THREADS) instnorm_fwd_kernel(const INFwdAr
 #pragma unroll
     for (int k = 0; k < NV; ++k) s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
     const float invT = 1.0f / (float)a.T;
-    const float mean = group_sum<LPR>(s) * invT;
+    const float mean = group_sum<LPR>(s) / (float)a.T;   // a division: see in_xhat (avc_common.h)
     float ss = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(AVC_THREADS) instnorm_fwd_generic_kernel(const
     float s = 0.f;
     for (int t = l; t < a.T; t += 64) s += yrow[t];
     const float invT = 1.0f / (float)a.T;
-    const float mean = group_sum<64>(s) * invT;
+    const float mean = group_sum<64>(s) / (float)a.T;   // see in_xhat
     float ss = 0.f;
     for (int t = l; t < a.T; t += 64) {
         float d = yrow[t] - mean;
@@ -534,7 +534,7 @@ __global__ void __launch_bounds__(AVC_THREADS) clip_adam_kernel(const AdamArgs a
     float total = block_sum(s, red);
     float gnorm = sqrtf(total) * a.grad_prescale;   // grads are (sum over ranks) * grad_prescale
     float coef = a.max_norm / (gnorm + 1e-6f);      // clip_grad_norm_: min(1, max_norm/(norm+1e-6))
-    coef = fminf(coef, 1.0f);
+    coef = coef > 1.0f ? 1.0f : coef;               // (not fminf: a NaN norm stays the coefficient, as in the reference -- every parameter turns NaN)
     if (a.max_norm <= 0.f) coef = 1.0f;
     coef *= a.grad_prescale;
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.gnorm_out) a.gnorm_out[0] = gnorm;
@@ -558,7 +558,7 @@ __global__ void __launch_bounds__(AVC_THREADS) clip_adam_kernel(const AdamArgs a
                 const float v = a.beta2 * vv[k] + (1.0f - a.beta2) * g * g;
                 float denom;
                 if (a.amsgrad) {
-                    const float vm = fmaxf(xx[k], v);
+                    const float vm = xx[k] >= v ? xx[k] : v;   // a NaN v propagates as in torch.maximum (fmaxf would drop it; v stays NaN from then on)
                     xx[k] = vm;
                     denom = sqrtf(vm) / a.sqrt_bc2 + a.eps;
                 } else {
@@ -585,7 +585,8 @@ __global__ void __launch_bounds__(AVC_THREADS) clip_adam_kernel(const AdamArgs a
         float v = a.beta2 * a.v[e] + (1.0f - a.beta2) * g * g;
         float denom;
         if (a.amsgrad) {
-            float vm = fmaxf(a.vmax[e], v);
+            const float vx = a.vmax[e];
+            float vm = vx >= v ? vx : v;
             a.vmax[e] = vm;
             denom = sqrtf(vm) / a.sqrt_bc2 + a.eps;
         } else {

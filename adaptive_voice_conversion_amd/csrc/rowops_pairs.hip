@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(AVC_THREADS) instnorm_fwd_pairs_kernel(const I
         s1 += (vh[k][0] + vh[k][1]) + (vh[k][2] + vh[k][3]);
     }
     const float invT = 1.0f / (float)a.T;
-    const float mean0 = group_sum<LPR>(s0) * invT, mean1 = group_sum<LPR>(s1) * invT;
+    const float mean0 = group_sum<LPR>(s0) / (float)a.T, mean1 = group_sum<LPR>(s1) / (float)a.T;   // see in_xhat
     float q0 = 0.f, q1 = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
