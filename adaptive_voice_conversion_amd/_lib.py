@@ -102,6 +102,10 @@ def declare(lib):
         lib.avc_plan_create_ragged_content_grads.argtypes = [ctypes.POINTER(ModelCfg), c_int, ctypes.POINTER(c_int), ctypes.POINTER(Tuning),
                                                              ctypes.POINTER(c_void_p)]
         lib.avc_content_backward_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    if hasattr(lib, "avc_plan_create_ragged_decoder_grads"):   # (likewise)
+        lib.avc_plan_create_ragged_decoder_grads.argtypes = [ctypes.POINTER(ModelCfg), c_int, ctypes.POINTER(c_int), ctypes.POINTER(Tuning),
+                                                             ctypes.POINTER(c_void_p)]
+        lib.avc_decoder_backward_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p]
     lib.avc_gather_segments.argtypes = [c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.avc_plan_destroy.argtypes = [c_void_p]
     lib.avc_plan_destroy.restype = None

@@ -256,6 +256,12 @@ struct RagINBwdArgs {
     const int* off;
     int B, C;
     float slope;
+    // AdaIN rows (the decoder; cond == null: plain InstanceNorm, nothing below is read)
+    const float* cond;  // AdaIN affine [B][cond_sb]: beta = cond[off + c], gamma = cond[off + C + c]
+    float* dcond;       // same layout: d(beta) -> [off + c], d(gamma) -> [off + C + c]
+    long cond_sb;
+    int cond_off;
+    int up;             // > 1: planar store, frame t of row c -> row c * up + t % up, frame t / up of the sample's [C * up][T_b / up] block
 };
 
 struct INBwdArgs {

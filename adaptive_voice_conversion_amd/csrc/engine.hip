@@ -2065,6 +2065,14 @@ extern "C" int avc_plan_create_ragged_content_grads(const avc_model_cfg* cfg, in
     return rag_plan_create(cfg, S, T, nullptr, AVC_PLAN_FANOUT | AVC_PLAN_CONTENT_ONLY | AVC_PLAN_INPUT_GRADS, 0, nullptr, tuning, out);
 }
 
+// The decoder alone over N latents WITH a backward pass with respect to its two inputs (avc_decoder_backward_ragged): output j from latent j
+// (the identity map: no AVC_PLAN_FANOUT), the forward launches of the decoder-only fan-out plan over the same lengths, plus the
+// input-gradient weight images, the saved InstanceNorm statistics, d(cond), the gradient rows, d(z) and d(emb).
+extern "C" int avc_plan_create_ragged_decoder_grads(const avc_model_cfg* cfg, int N, const int* Tz, const avc_tuning* tuning, avc_plan** out) {
+    if (!cfg || !out || !Tz || N < 1) return fail(-1, "avc_plan_create_ragged_decoder_grads: bad arguments (N >= 1 latents of Tz[j] frames)");
+    return rag_plan_create(cfg, N, Tz, nullptr, AVC_PLAN_EMB_INPUT | AVC_PLAN_DECODER_ONLY | AVC_PLAN_INPUT_GRADS, 0, nullptr, tuning, out);
+}
+
 // flags: what avc_plan_flags reports, minus INFERENCE | RAGGED.  With AVC_PLAN_FANOUT the decoder runs over N samples mapped onto the B
 // sources by src_of; without it over the B sources themselves.
 static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, int flags, int N, const int* src_of,
@@ -2213,13 +2221,14 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
     const avc_plan::RagLevel* lz = do_dec ? (fan ? &p->rl_z : &p->rl_dec[0]) : (do_enc ? &p->rl_enc[p->enc.n] : nullptr);
     if (do_enc) finish_layer(p, p->layers[p->enc.heads], ig, 0, p->rl_enc[p->enc.n].ntiles, 64, 64);
     if (do_dec) {
-        finish_layer(p, p->layers[d.in_conv], false, 0, lz->ntiles, 64, 64);
+        // (ig: the plan of avc_plan_create_ragged_decoder_grads adds the input-gradient images)
+        finish_layer(p, p->layers[d.in_conv], ig, 0, lz->ntiles, 64, 64);
         for (int l = 0; l < d.n; ++l) {
-            finish_layer(p, p->layers[d.c1[l]], false, 0, p->rl_dec[l].ntiles, 64, 64);
-            finish_layer(p, p->layers[d.c2[l]], false, 0, p->rl_dec[l].ntiles, 64, 64);
+            finish_layer(p, p->layers[d.c1[l]], ig, 0, p->rl_dec[l].ntiles, 64, 64);
+            finish_layer(p, p->layers[d.c2[l]], ig, 0, p->rl_dec[l].ntiles, 64, 64);
         }
-        finish_layer(p, p->layers[d.affine], false, 0, 1, Nd, Nd);
-        finish_layer(p, p->layers[d.out_conv], false, 0, p->rl_dec[d.n].ntiles, 64, 64);
+        finish_layer(p, p->layers[d.affine], ig, 0, 1, Nd, Nd);
+        finish_layer(p, p->layers[d.out_conv], ig, 0, p->rl_dec[d.n].ntiles, 64, 64);
     }
 
     // ---- packed activation buffers: [channels][T_b] blocks back to back
@@ -2326,6 +2335,34 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
         p->decb = p->alloc((long)p->M * p->rl_dec[d.n].off[Nd]);
         p->named["dec"] = p->decb;
         p->named["cond"] = d.cond;
+    }
+    if (ig && do_dec) {   // avc_decoder_backward_ragged: row statistics of every InstanceNorm, d(cond), two ping-pong pairs of gradient rows, d(z), d(emb)
+        const long Nl = Nd, top = p->rl_dec[d.n].off[Nd];   // (the last level is the longest: upsample factors are 1 or 2)
+        d.st0 = p->alloc(2 * Nl * Cd);   // mean[N * C] | rstd[N * C], row b * C + c
+        for (int l = 0; l < d.n; ++l) {
+            d.st1[l] = p->alloc(2 * Nl * Cd);
+            d.st2[l] = p->alloc(2 * Nl * Cd);
+        }
+        d.dcond = p->alloc(Nl * 2 * d.n * 2 * Cd);
+        p->gA2 = p->alloc(Cd * top);    // G_l: d(loss)/d(out_l), the residual path's gradient
+        p->gC2 = p->alloc(Cd * top);
+        p->gA = p->alloc(Cd * top);     // d(y): what an AdaIN backward leaves for the conv's input gradient
+        p->gB = p->alloc(Cd * top);     // d(a1): conv2's input gradient
+        p->dz = p->alloc(Cz * lz->off[B]);
+        p->demb_rm = p->alloc(Nl * dc.c_cond);
+        p->named["d_z"] = p->dz;
+        p->named["d_emb"] = p->demb_rm;
+        p->named["d_cond"] = d.dcond;
+        // what the backward pass masks by (tests read the activation branch the engine took from the saved rows and statistics)
+        p->named["dec_y0"] = d.y0;
+        p->named["dec_st0"] = d.st0;
+        for (int l = 0; l < d.n; ++l) {
+            p->named["dec_y1_" + std::to_string(l)] = d.y1[l];
+            p->named["dec_a1_" + std::to_string(l)] = d.a1[l];
+            p->named["dec_y2_" + std::to_string(l)] = d.y2[l];
+            p->named["dec_st1_" + std::to_string(l)] = d.st1[l];
+            p->named["dec_st2_" + std::to_string(l)] = d.st2[l];
+        }
     }
     p->rag_tab = p->alloc((long)p->rag_host.size());
     plan_init_streams(p);
@@ -2541,6 +2578,8 @@ static int rag_forward_impl(const avc_plan* p, const float* params, const float*
         const int Nd = p->Nd;
         const float* es = emb ? emb : ws + p->emb;
         const long esb = emb ? seb : d.c.c_cond, esc = emb ? sec : 1;
+        const bool keep_stats = (p->flags & AVC_PLAN_INPUT_GRADS) != 0;   // (avc_plan_create_ragged_decoder_grads plans: the row statistics stay)
+        auto st = [&](long off) -> float* { return keep_stats ? ws + off : nullptr; };
         {   // all 2n AdaIN affine Linears as ONE GEMM on emb (uniform: one row per utterance; esb = 0: every utterance reads the same row)
             ConvArgs a = mk_fwd(p, SL, p->layers[d.affine], params, ws, es, 0, esc, (int)esb, 1, Nd, ws + d.cond, 0, 1, (int)csb, 0);
             RUN(avc_launch_conv(a, s, 0, p->tun));
@@ -2548,19 +2587,19 @@ static int rag_forward_impl(const avc_plan* p, const float* params, const float*
         {   // z = mu: the first Cz channels of every sample's (mu | log_sigma) block
             ConvArgs a = conv(SL, p->layers[d.in_conv], z ? z : ws + p->muls, lz, z ? zc : 2 * Cz, ws + d.y0, lz, lz, C, 0, 1);
             RUN(avc_launch_conv(a, s, 0, p->tun));
-            RUN(rag_in(B, SL, tab, ws + d.y0, ws + d.out[0], lz, C, nullptr, 0, 0, nullptr, 0, nullptr, s));
+            RUN(rag_in(B, SL, tab, ws + d.y0, ws + d.out[0], lz, C, nullptr, 0, 0, nullptr, 0, nullptr, s, st(d.st0)));
         }
         for (int l = 0; l < d.n; ++l) {
             const int up = d.c.upsample[l];
             const avc_plan::RagLevel& lin = l == 0 ? lm : lv[l];   // where out[l] lies: block 0 reads the sources' blocks
             ConvArgs a = conv(SL, p->layers[d.c1[l]], ws + d.out[l], lin, C, ws + d.y1[l], lv[l], lv[l], C, 0, 1);
             RUN(avc_launch_conv(a, s, 0, p->tun));
-            RUN(rag_in(Nd, SL, tab, ws + d.y1[l], ws + d.a1[l], lv[l], C, ws + d.cond, csb, (2 * l) * 2 * C, nullptr, 0, nullptr, s));
+            RUN(rag_in(Nd, SL, tab, ws + d.y1[l], ws + d.a1[l], lv[l], C, ws + d.cond, csb, (2 * l) * 2 * C, nullptr, 0, nullptr, s, st(d.st1[l])));
             // second conv: C * up channels, pixel-shuffled on store into the level-(l+1) buffer (model.py:359-361)
             ConvArgs b = conv(SL, p->layers[d.c2[l]], ws + d.a1[l], lv[l], C, ws + d.y2[l], lv[l], lv[l + 1], C, 0, up);
             RUN(avc_launch_conv(b, s, 0, p->tun));
             RUN(rag_in(Nd, SL, tab, ws + d.y2[l], ws + d.out[l + 1], lv[l + 1], C, ws + d.cond, csb, (2 * l + 1) * 2 * C, ws + d.out[l],
-                       up > 1 ? AVC_RES_UP2 : AVC_RES_IDENTITY, &lin, s));
+                       up > 1 ? AVC_RES_UP2 : AVC_RES_IDENTITY, &lin, s, st(d.st2[l])));
         }
         ConvArgs o = conv(SL, p->layers[d.out_conv], ws + d.out[d.n], lv[d.n], C, ws + p->decb, lv[d.n], lv[d.n], p->M, 0, 1);
         RUN(avc_launch_conv(o, s, 0, p->tun));
@@ -2809,4 +2848,98 @@ extern "C" int avc_content_backward_ragged(const avc_plan* p, const float* param
         return fail(-8, "avc_content_backward_ragged: the avc_plan_create_ragged_content_grads plan computes with bf16 operand rounding, a forward-only model; "
                         "gradients need fp32 (avc_plan_set_compute_dtype(p, 0)) or a uniform plan");
     return rag_content_backward_impl(p, d_muls, ws, (hipStream_t)stream);
+}
+
+// The backward pass of a plan of avc_plan_create_ragged_decoder_grads: d(loss)/d(z) and d(loss)/d(emb) from d(loss)/d(dec), parameters
+// frozen.  One branch on the caller's stream, the uniform decoder chain of avc_backward_impl minus every weight gradient:
+//   d_dec -> out_conv^T -> per block, last to first: AdaIN-bwd(y2) (planar store where the block upsamples: the rows leave as the conv's
+//   own [C up][T_l] output rows) -> conv2^T -> AdaIN-bwd(y1) -> conv1^T with the nearest-upsampling / identity adjoint of the residual path
+//   in its epilogue join -> IN-bwd(y0) -> in_conv^T into ws["d_z"] ([c_in][Tz_s] blocks) -> d(emb) = W_affine^T d(cond), one uniform
+//   input-gradient launch over N columns that stores row-major [N][c_cond] into ws["d_emb"].
+// 1 + 4 n + 2 + 1 launches (28 for the stock 6 blocks): every AdaIN backward writes its [N][2 C] slice of d(cond) once, nothing is zeroed.
+static int rag_decoder_backward_impl(const avc_plan* p, const float* d_dec, float* ws, hipStream_t s) {
+    const int N = p->Nd;
+    const DecNet& d = p->dec;
+    const float SL = d.slope;
+    const std::vector<avc_plan::RagLevel>& lv = p->rl_dec;
+    const int C = d.c.c_h, Cz = d.c.c_in;
+    const long csb = (long)2 * d.n * 2 * C;
+    const int* tab = (const int*)(ws + p->rag_tab);
+    float* gA = ws + p->gA2;
+    float* gC = ws + p->gC2;
+    float* dyA = ws + p->gA;
+    float* dyB = ws + p->gB;
+    // (every ragged launch below asks for the 64 x 64 tile: a ragged tile is one sample's 64 frames, the mirrored instances exist on that tile only)
+    auto dgrad = [&](const LayerP& L, const float* dy, const avc_plan::RagLevel& sl, int cx, float* dx, const avc_plan::RagLevel& ol, int cout) {
+        ConvArgs a = mk_dgrad(SL, L, ws, dy, 0, -1, 1, 1, 1, 0, 64, dx, 0, 0, 1);
+        set_rag(a, tab, sl, cx, ol, ol, cout);
+        return a;
+    };
+    // coff < 0: plain InstanceNorm (the in_conv stage); up: planar store factor
+    auto in_bwd_rows = [&](const float* g, long y, long st, const avc_plan::RagLevel& l, int coff, int up, float* dy) {
+        RagINBwdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.g = g; a.y = ws + y; a.mean = ws + st; a.rstd = ws + st + (long)N * C; a.dy = dy;
+        a.T = tab + l.dT; a.off = tab + l.doff;
+        a.B = N; a.C = C; a.slope = SL;
+        if (coff >= 0) { a.cond = ws + d.cond; a.dcond = ws + d.dcond; a.cond_sb = csb; a.cond_off = coff; a.up = up; }
+        return avc_launch_rag_in_bwd(a, s);
+    };
+    {   // G_n = out_conv^T(d_dec): the caller's [M][T''_j] blocks
+        ConvArgs a = dgrad(p->layers[d.out_conv], d_dec, lv[d.n], p->M, gA, lv[d.n], C);
+        RUN(avc_launch_conv(a, s, 11, p->tun));
+    }
+    for (int l = d.n - 1; l >= 0; --l) {
+        const int up = d.c.upsample[l];
+        RUN(in_bwd_rows(gA, d.y2[l], d.st2[l], lv[l + 1], (2 * l + 1) * 2 * C, up, dyA));
+        {   // d(a1) = conv2^T(d(y2)): d(y2) lies as the conv's own output rows [C up][T_l] (C up off_l == C off_{l+1}: the same block starts)
+            ConvArgs a = dgrad(p->layers[d.c2[l]], dyA, lv[l], C * up, dyB, lv[l], C);
+            RUN(avc_launch_conv(a, s, 11, p->tun));
+        }
+        RUN(in_bwd_rows(dyB, d.y1[l], d.st1[l], lv[l], (2 * l) * 2 * C, 1, dyA));
+        {   // G_l = conv1^T(d(y1)) + up^T(G_{l+1})
+            ConvArgs a = dgrad(p->layers[d.c1[l]], dyA, lv[l], C, gC, lv[l], C);
+            set_rag_res(a, tab, gA, up > 1 ? AVC_RES_UPT : AVC_RES_IDENTITY, lv[l + 1], C);
+            RUN(avc_launch_conv(a, s, 11, p->tun));
+        }
+        float* t = gA; gA = gC; gC = t;
+    }
+    RUN(in_bwd_rows(gA, d.y0, d.st0, lv[0], -1, 1, dyA));
+    {   // d(z): blocks [c_in][Tz_s] at c_in * offz[s]
+        ConvArgs a = dgrad(p->layers[d.in_conv], dyA, lv[0], C, ws + p->dz, lv[0], Cz);
+        RUN(avc_launch_conv(a, s, 11, p->tun));
+    }
+    {   // d(emb)[b][i] = sum_o W[o][i] d(cond)[b][o]: the stacked affine layer's input gradient, "frames" = the N samples (d(cond) read with
+        // channel stride 1, frame stride csb), stored row-major through the output strides -- the mirror image of the forward affine launch
+        const LayerP& La = p->layers[d.affine];
+        ConvArgs a = mk_dgrad(SL, La, ws, ws + d.dcond, 0, 1, (int)csb, 1, 1, N, N, ws + p->demb_rm, 0, 1, d.c.c_cond);
+        RUN(avc_launch_conv(a, s, 0, p->tun));
+    }
+    return 0;
+}
+
+// z / zc / emb / seb / sec: what the avc_decoder_forward_ragged this pass follows was given (the frozen-parameter pass reads the saved rows,
+// not the inputs; they are checked like the forward's).  d_dec: packed [M][T''_j] blocks, the layout avc_plan_ragged_out reports (block j at
+// M * sum of the output lengths before it).  Results: ws["d_z"] (blocks [c_in][Tz_s] at c_in * offz[s]) and ws["d_emb"] ([N][c_cond],
+// always dense).  Allocates nothing, synchronises nothing: every launch goes to the caller's stream.
+extern "C" int avc_decoder_backward_ragged(const avc_plan* p, const float* params, const float* z, int zc, const float* emb, long seb, long sec,
+                                           const float* d_dec, float* ws, void* stream) {
+    if (!p || !params || !z || !emb || !d_dec || !ws)
+        return fail(-1, "avc_decoder_backward_ragged: null argument (pass the avc_plan_create_ragged_decoder_grads plan, params, z, emb and workspace of the "
+                        "avc_decoder_forward_ragged this pass follows, and d_dec)");
+    if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_INPUT_GRADS))
+        return fail(-8, "avc_decoder_backward_ragged: the plan was not created by avc_plan_create_ragged_decoder_grads");
+    if (p->flags & AVC_PLAN_FANOUT)
+        return fail(-8, "avc_decoder_backward_ragged: fan-out plans (AVC_PLAN_FANOUT) have no decoder backward pass; create the plan with "
+                        "avc_plan_create_ragged_decoder_grads (output j from latent j) and index the latents in the caller");
+    if (!(p->flags & AVC_PLAN_DECODER_ONLY))
+        return fail(-8, "avc_decoder_backward_ragged: the plan was not created by avc_plan_create_ragged_decoder_grads");
+    if (p->compute != AVC_COMPUTE_F32)
+        return fail(-8, "avc_decoder_backward_ragged: the avc_plan_create_ragged_decoder_grads plan computes with bf16 operand rounding, a forward-only model; "
+                        "gradients need fp32 (avc_plan_set_compute_dtype(p, 0)) or a uniform plan (avc_decoder_backward)");
+    if (zc < p->cfg.dec.c_in)
+        return fail(-1, "avc_decoder_backward_ragged: zc is too small: a latent block has at least c_in rows");
+    if (seb < 0 || sec < 0 || (p->Nd - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
+        return fail(-1, "avc_decoder_backward_ragged: emb strides must be non-negative and span less than 2^31 elements");
+    return rag_decoder_backward_impl(p, d_dec, ws, (hipStream_t)stream);
 }

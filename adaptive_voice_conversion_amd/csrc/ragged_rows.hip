@@ -1,5 +1,5 @@
 // Row / glue kernels of the RAGGED passes (forward; backward of the speaker encoder: avc_backward_ragged; backward of the content encoder:
-// avc_content_backward_ragged) (AE.inference over utterances of different lengths in one launch set;
+// avc_content_backward_ragged; backward of the decoder: avc_decoder_backward_ragged) (AE.inference over utterances of different lengths in one launch set;
 // reference: inference.py:54-70, model.py:387-391 -- the reference converts one utterance per call).
 //
 // Packed buffers: sample b owns a contiguous [channels][T_b] block starting at element channels * off[b] (off = prefix sums
@@ -70,10 +70,16 @@ __global__ void __launch_bounds__(AVC_THREADS) rag_instnorm_fwd_kernel(const Rag
     }
 }
 
-// Backward of rag_instnorm_fwd_kernel without AdaIN (gamma = 1, beta = 0: the content encoder): one wavefront per row (b, c), two passes
-// over the row's own T_b frames -- the sums of g and g * xhat (per-lane partial sums in frame order, then the fixed butterfly of wave_sum:
-// no atomics), then dy = rstd * (g - mean_t(g) - xhat * mean_t(g * xhat)).  g = G masked by the forward's ReLU decision: xhat / preact
-// come from the SAVED statistics through in_xhat / in_preact, bit for bit the forward's (instnorm_bwd_generic_kernel of rowops.hip).
+// Backward of rag_instnorm_fwd_kernel: one wavefront per row (b, c), two passes over the row's own T_b frames -- the sums of g and g * xhat
+// (per-lane partial sums in frame order, then the fixed butterfly of wave_sum: no atomics), then
+// dy = rstd * gamma * (g - mean_t(g) - xhat * mean_t(g * xhat)).  g = G masked by the forward's activation decision: xhat / preact come from
+// the SAVED statistics through in_xhat / in_preact, bit for bit the forward's (instnorm_bwd_generic_kernel of rowops.hip).
+// ADA = false (the content encoder: gamma = 1, beta = 0): nothing below reads cond / dcond / up, the instance is the kernel the content
+// plan always ran.  ADA = true (the decoder's AdaIN rows): gamma / beta from cond in the layout the forward reads; lane 0 stores the row's
+// two sums as d(beta), d(gamma) into dcond (same [B][cond_sb] layout; every element written once per pass); up > 1: the PLANAR store behind a
+// pixel-shuffling conv (model.py:52-59) -- frame t of row c goes to conv-output row c * up + t % up, frame t / up of the sample's block, which
+// is then [C * up][T_b / up]: the conv's input gradient reads a plain stride-1 packed source.
+template <bool ADA>
 __global__ void __launch_bounds__(AVC_THREADS) rag_instnorm_bwd_kernel(const RagINBwdArgs a) {
     const int tid = threadIdx.x, l = tid & 63;
     const int row = blockIdx.x * 4 + (tid >> 6);
@@ -84,20 +90,45 @@ __global__ void __launch_bounds__(AVC_THREADS) rag_instnorm_bwd_kernel(const Rag
     const float* yrow = a.y + base;
     const float* grow = a.g + base;
     const float mean = a.mean[row], rstd = a.rstd[row];
+    float gamma = 1.f, beta = 0.f;
+    if constexpr (ADA) {
+        const float* cr = a.cond + (long)b * a.cond_sb + a.cond_off;
+        beta = cr[c];
+        gamma = cr[a.C + c];
+    }
     float s1 = 0.f, s2 = 0.f;
     for (int t = l; t < T; t += 64) {
         const float h = in_xhat(yrow[t], mean, rstd);
-        const float gme = avc_act_grad(grow[t], in_preact(h, 1.f, 0.f) > 0.f, a.slope);
+        const float gme = avc_act_grad(grow[t], in_preact(h, gamma, beta) > 0.f, a.slope);
         s1 += gme;
         s2 += gme * h;
     }
     const float invT = 1.0f / (float)T;
-    const float m1 = wave_sum(s1) * invT, m2 = wave_sum(s2) * invT;
-    float* drow = a.dy + base;
-    for (int t = l; t < T; t += 64) {
-        const float h = in_xhat(yrow[t], mean, rstd);
-        const float gme = avc_act_grad(grow[t], in_preact(h, 1.f, 0.f) > 0.f, a.slope);
-        drow[t] = rstd * (gme - m1 - h * m2);
+    if constexpr (!ADA) {
+        const float m1 = wave_sum(s1) * invT, m2 = wave_sum(s2) * invT;
+        float* drow = a.dy + base;
+        for (int t = l; t < T; t += 64) {
+            const float h = in_xhat(yrow[t], mean, rstd);
+            const float gme = avc_act_grad(grow[t], in_preact(h, 1.f, 0.f) > 0.f, a.slope);
+            drow[t] = rstd * (gme - m1 - h * m2);
+        }
+    } else {
+        s1 = wave_sum(s1);
+        s2 = wave_sum(s2);
+        if (l == 0) {
+            float* dc = a.dcond + (long)b * a.cond_sb + a.cond_off;
+            dc[c] = s1;
+            dc[a.C + c] = s2;
+        }
+        const float m1 = s1 * invT, m2 = s2 * invT, rg = rstd * gamma;
+        const int up = a.up > 1 ? a.up : 1, Tc = T / up;   // (T_b is a multiple of up: the level behind an upsampling block)
+        float* dblk = a.dy + (long)a.C * a.off[b];
+        for (int t = l; t < T; t += 64) {
+            const float h = in_xhat(yrow[t], mean, rstd);
+            const float gme = avc_act_grad(grow[t], in_preact(h, gamma, beta) > 0.f, a.slope);
+            const int tc = t / up;
+            dblk[(long)(c * up + (t - tc * up)) * Tc + tc] = rg * (gme - m1 - h * m2);
+        }
     }
 }
 
@@ -185,7 +216,8 @@ int avc_launch_rag_in_fwd(const RagINArgs& a, hipStream_t s) {
 }
 int avc_launch_rag_in_bwd(const RagINBwdArgs& a, hipStream_t s) {
     ProfScope ps(AVC_K_IN_BWD, 0.0, 0.0, s);
-    hipLaunchKernelGGL(rag_instnorm_bwd_kernel, dim3(avc_cdiv(a.B * a.C, 4)), dim3(AVC_THREADS), 0, s, a);
+    if (a.cond) hipLaunchKernelGGL((rag_instnorm_bwd_kernel<true>), dim3(avc_cdiv(a.B * a.C, 4)), dim3(AVC_THREADS), 0, s, a);
+    else hipLaunchKernelGGL((rag_instnorm_bwd_kernel<false>), dim3(avc_cdiv(a.B * a.C, 4)), dim3(AVC_THREADS), 0, s, a);
     return (int)hipGetLastError();
 }
 int avc_launch_rag_copy_rows(const float* x, long xsc, long xst, const int* T, const int* off, int B, int M, int sumT, float* dst, int CC, int c0,

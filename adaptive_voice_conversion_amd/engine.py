@@ -306,7 +306,7 @@ class Plan:
 
 class RaggedPlan:
     """Launch plan of ONE pass over B utterances of DIFFERENT lengths (avc_plan_create_ragged_ex).  Nothing is padded.  Forward only,
-    except a "speaker" or an "encode" plan created with ``input_grads=True`` (below).
+    except a "speaker" or an "encode" plan created with ``input_grads=True`` and a "decode_ig" plan (below).
 
     mode "pairs" (default): B (source, target) pairs through all three networks, the batched form of
     ``Inferencer.inference_one_utterance`` (inference.py:54-70); result b equals ``AE.inference(x_b, x_cond_b)`` (model.py:387-391).
@@ -333,7 +333,15 @@ class RaggedPlan:
     mode "fanout": content encoder over the S sources ONCE, decoder over the N outputs: ``forward_emb(params, x, emb, ws)`` with x
     [sum T, M] (each source once) and emb [N, c_cond]; output j equals ``decoder(content_encoder(x_{src_of[j]})[0], emb_j)``.
     mode "encode": the content encoder alone (``src_of`` must be None): ``forward(params, x, None, ws)``, then ``latents(ws)``.
-    mode "decode": the decoder alone from the caller's latents; ``T`` are the LATENT lengths: ``forward_latents(params, z, zc, emb, ws)``."""
+    mode "decode": the decoder alone from the caller's latents; ``T`` are the LATENT lengths: ``forward_latents(params, z, zc, emb, ws)``.
+
+    mode "decode_ig" (avc_plan_create_ragged_decoder_grads; ``input_grads`` is implied): the "decode" plan with the identity map
+    (output j from latent j, no ``src_of``) and a backward pass with respect to its two inputs, parameters frozen, fp32 only: after
+    ``forward_latents(params, z, zc, emb, ws)``, ``backward_decoder(params, z, zc, emb, d_dec, ws)`` leaves d(loss)/d(z) in ``d_z(ws)``
+    and d(loss)/d(emb) in ``d_emb(ws)``.  Forward bit-identical to the "decode" plan; a larger workspace (weight images, row statistics,
+    d(cond), gradient rows).  ``buffer()`` names of the saved rows: "dec_y0", "dec_y1_<l>", "dec_a1_<l>", "dec_y2_<l>", their statistics
+    "dec_st0", "dec_st1_<l>", "dec_st2_<l>", and "cond" / "d_cond".  (``mode="decode", input_grads=True`` keeps raising: fan-out plans,
+    with their free ``src_of``, are forward only.)"""
 
     MODES = {"pairs": 0, "speaker": _lib.PLAN_SPEAKER_ONLY, "emb": _lib.PLAN_EMB_INPUT}
     FAN_MODES = {"fanout": 0, "encode": _lib.PLAN_CONTENT_ONLY, "decode": _lib.PLAN_DECODER_ONLY}
@@ -342,14 +350,20 @@ class RaggedPlan:
                  src_of=None):
         self.lib = lib if lib is not None else _lib.load()
         self.cfg = cfg_from_dict(config)
-        if mode not in self.MODES and mode not in self.FAN_MODES:
-            raise ValueError(f"mode must be one of {sorted(self.MODES) + sorted(self.FAN_MODES)}, got {mode!r}")
+        if mode not in self.MODES and mode not in self.FAN_MODES and mode != "decode_ig":
+            raise ValueError(f"mode must be one of {sorted(self.MODES) + sorted(self.FAN_MODES) + ['decode_ig']}, got {mode!r}")
         self.mode = mode
-        self.input_grads = bool(input_grads)
+        self.input_grads = bool(input_grads) or mode == "decode_ig"
         self.src_of = None
         if src_of is not None and mode not in ("fanout", "decode"):
             raise ValueError(f"src_of belongs to plans of mode 'fanout' or 'decode' (this one is {mode!r})")
-        if mode in self.FAN_MODES:
+        if mode == "decode_ig":
+            if not hasattr(self.lib, "avc_plan_create_ragged_decoder_grads"):
+                raise RuntimeError("the loaded library has no avc_plan_create_ragged_decoder_grads")
+            self.T = [int(t) for t in (T if T is not None else [])]
+            self.T_cond = []
+            self.B = len(self.T)
+        elif mode in self.FAN_MODES:
             if self.input_grads and mode != "encode":
                 raise ValueError("fan-out plans are forward only (input_grads belongs to mode='speaker')")
             if self.input_grads and not hasattr(self.lib, "avc_plan_create_ragged_content_grads"):
@@ -388,7 +402,9 @@ class RaggedPlan:
         self.N = len(self.src_of) if self.src_of is not None else (0 if mode == "encode" else self.B)
         dev = torch.device(device) if device is not None else None
         with (torch.cuda.device(dev) if (dev is not None and dev.type == "cuda") else contextlib.nullcontext()):
-            if mode == "encode" and self.input_grads:
+            if mode == "decode_ig":
+                rc = self.lib.avc_plan_create_ragged_decoder_grads(ctypes.byref(self.cfg), self.B, arr(*self.T), ctypes.byref(tun), ctypes.byref(h))
+            elif mode == "encode" and self.input_grads:
                 rc = self.lib.avc_plan_create_ragged_content_grads(ctypes.byref(self.cfg), self.B, arr(*self.T), ctypes.byref(tun), ctypes.byref(h))
             elif mode in self.FAN_MODES:
                 rc = self.lib.avc_plan_create_ragged_fanout(ctypes.byref(self.cfg), self.B, arr(*self.T), self.N,
@@ -422,7 +438,7 @@ class RaggedPlan:
                 raise RuntimeError(self.lib.avc_last_error().decode())
             self.out_len, self.out_off = list(lens), list(offs)
         self.lat_len, self.lat_off = [], []   # per SOURCE: latent frames and the float offset of its (mu | log_sigma) block in ws["muls"]
-        if mode not in ("speaker", "decode") and hasattr(self.lib, "avc_plan_ragged_latents"):
+        if mode not in ("speaker", "decode", "decode_ig") and hasattr(self.lib, "avc_plan_ragged_latents"):
             lens, offs = (ctypes.c_int * self.B)(), (ctypes.c_long * self.B)()
             if self.lib.avc_plan_ragged_latents(h, lens, offs) != 0:
                 raise RuntimeError(self.lib.avc_last_error().decode())
@@ -445,7 +461,7 @@ class RaggedPlan:
         A "speaker" plan reads x_cond only (pass x = None)."""
         if self.mode in ("emb", "fanout"):
             raise RuntimeError(f"an {self.mode!r} plan has no speaker encoder: call forward_emb(params, x, emb, ws)")
-        if self.mode == "decode":
+        if self.mode in ("decode", "decode_ig"):
             raise RuntimeError("a 'decode' plan starts from latents: call forward_latents(params, z, zc, emb, ws)")
         if self.mode == "encode":
             if x_cond is not None:
@@ -484,17 +500,49 @@ class RaggedPlan:
         """"decode" plans: z holds the S latent blocks back to back, block s = [zc][T[s]] fp32 (frames contiguous) at float offset
         zc * sum(T[:s]); the first c_lat channels of a block are read in place.  zc = c_lat: mu-only blocks; zc = 2 c_lat: the
         ws["muls"] region of a plan with a content encoder over the same sources, passed as it is.  emb: [N, c_cond] as in ``forward_emb``."""
-        if self.mode != "decode":
+        if self.mode not in ("decode", "decode_ig"):
             raise RuntimeError(f"forward_latents needs a plan of mode 'decode' (this one is {self.mode!r})")
+        z, zc, emb = self._latents(z, zc, emb, ws)
+        with _on(ws):
+            self._chk(self.lib.avc_decoder_forward_ragged(self.h, _ptr(params), _ptr(z), zc, _ptr(emb), emb.stride(0), emb.stride(1), _ptr(ws),
+                                                          _stream(ws)))
+
+    def _latents(self, z, zc, emb, ws):
         zc = int(zc)
         if zc < self.c_lat:
             raise ValueError(f"zc must be at least {self.c_lat} ({self.c_lat}: mu-only blocks; {2 * self.c_lat}: mu | log_sigma blocks), got {zc}")
         if z.dtype != torch.float32 or z.device != ws.device or not z.is_contiguous() or z.numel() < zc * sum(self.T):
             raise ValueError(f"z must be a contiguous fp32 tensor of at least {zc * sum(self.T)} elements on {ws.device}")
-        emb = self._emb(emb, ws)
+        return z, zc, self._emb(emb, ws)
+
+    def backward_decoder(self, params, z, zc, emb, d_dec, ws):
+        """``mode="decode_ig"`` plans, after ``forward_latents(params, z, zc, emb, ws)`` in the same workspace: d(loss)/d(z) and
+        d(loss)/d(emb) from d_dec = d(loss)/d(dec): fp32, contiguous, n_mels * sum(out_len) elements on the workspace's device, block j =
+        [n_mels][out_len[j]] at element n_mels * sum(out_len[:j]) -- the layout of the workspace region ``outputs(ws)`` views.  The results
+        are ``d_z(ws)`` and ``d_emb(ws)``.  No parameter gradients; two calls give identical bits."""
+        if self.mode != "decode_ig":
+            raise RuntimeError("backward_decoder needs RaggedPlan(mode='decode_ig') "
+                               f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
+        z, zc, emb = self._latents(z, zc, emb, ws)
+        n = self.n_mels * sum(self.out_len)
+        if d_dec.dtype != torch.float32 or d_dec.device != ws.device or not d_dec.is_contiguous() or d_dec.numel() != n:
+            raise ValueError(f"d_dec must be a contiguous fp32 tensor of {n} elements on {ws.device} (the layout of the plan's output blocks)")
         with _on(ws):
-            self._chk(self.lib.avc_decoder_forward_ragged(self.h, _ptr(params), _ptr(z), zc, _ptr(emb), emb.stride(0), emb.stride(1), _ptr(ws),
-                                                          _stream(ws)))
+            self._chk(self.lib.avc_decoder_backward_ragged(self.h, _ptr(params), _ptr(z), zc, _ptr(emb), emb.stride(0), emb.stride(1), _ptr(d_dec),
+                                                           _ptr(ws), _stream(ws)))
+
+    def d_z(self, ws):
+        """list of [c_lat, T[s]] views of d(loss)/d(z_s) in the workspace (after ``backward_decoder``)"""
+        off, c, out = self.buffer("d_z"), self.c_lat, []
+        for n in self.T:
+            out.append(ws[off:off + c * n].view(c, n))
+            off += c * n
+        return out
+
+    def d_emb(self, ws):
+        """[N, c_cond] view of d(loss)/d(emb) in the workspace (after ``backward_decoder``): one row per output, always dense"""
+        off = self.buffer("d_emb")
+        return ws[off:off + self.N * self.c_emb].view(self.N, self.c_emb)
 
     def latents(self, ws):
         """(list of mu, list of log_sigma): per SOURCE [c_lat, lat_len[s]] views of the content codes in the workspace (plans that run

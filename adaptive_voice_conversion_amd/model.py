@@ -377,6 +377,38 @@ class _RaggedContentFunction(torch.autograd.Function):
         return None, ctx.plan.d_x(ctx.ws).clone(), None
 
 
+class _RaggedDecoderFunction(torch.autograd.Function):
+    """``AE.decoder_ragged`` with autograd with respect to its two inputs (a "decode_ig" RaggedPlan), modelled on
+    ``_RaggedContentFunction``: the function's inputs are the packed latents (block s = [c_lat][Tz_s]) and the [N, c_emb] embeddings (an
+    expanded single voice included), its output the packed [M][T''_j] blocks.  Torch's own autograd carries d_z back through the
+    concatenation to every latent leaf and sums the rows of an expanded voice.  Parameters are frozen."""
+
+    @staticmethod
+    def forward(ctx, ae, z, e, Tz):
+        plan, entry = ae._ragged_plan("decode_ig", Tz, ())
+        ws = entry.ws
+        if entry.busy():
+            ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=z.device)   # private to this forward
+        token = _Token()
+        if ws is entry.ws:
+            entry.pending = weakref.ref(token)
+        plan.forward_latents(ae._flat, z, plan.c_lat, e, ws)
+        ctx.ae, ctx.plan, ctx.ws, ctx.token = ae, plan, ws, token
+        ctx.save_for_backward(z, e)
+        o = plan.out_off[0]
+        return ws[o:o + plan.n_mels * sum(plan.out_len)].clone()
+
+    @staticmethod
+    def backward(ctx, d_dec):
+        _PartFunction._check(ctx)
+        z, e = ctx.saved_tensors
+        plan, ws = ctx.plan, ctx.ws
+        plan.backward_decoder(ctx.ae._flat, z, plan.c_lat, e, d_dec.float().contiguous(), ws)
+        ctx.token.done = True
+        o = plan.buffer("d_z")
+        return None, ws[o:o + plan.c_lat * sum(plan.T)].clone(), plan.d_emb(ws).clone(), None
+
+
 class _ContentFunction(_PartFunction):
     """ContentEncoder.forward (model.py:301-323) with autograd; x gets its gradient when it requires one (a plan with
     AVC_PLAN_INPUT_GRADS)."""
@@ -610,8 +642,8 @@ class AE(nn.Module):
         return self._outputs(plan, ws)[2].clone()
 
     def _ragged_plan(self, mode, T, Tc, src_of=None):
-        """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all modes are kept.  modes "speaker_ig" and
-        "encode_ig" (the speaker / content plan with input gradients) return (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
+        """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all modes are kept.  modes "speaker_ig",
+        "encode_ig" and "decode_ig" (the speaker / content / decoder plan with input gradients) return (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
         activations between a forward and its backward and is never the pooled one.  ``src_of`` (a tuple; "fanout" / "decode" plans):
         the source of every output, part of the key."""
         from .engine import RaggedPlan
@@ -621,9 +653,9 @@ class AE(nn.Module):
         if hit is None:
             # compute_dtype "bf16" -> "bf16r" here: the pair-STORAGE engine takes uniform shapes only; ragged plans round the operands of
             # the matrix products to bf16 on fp32 storage (engine.RaggedPlan).  The mode that ran is reported in `last_ragged_compute`.
-            ig = mode in ("speaker_ig", "encode_ig")
+            ig = mode in ("speaker_ig", "encode_ig", "decode_ig")
             plan = RaggedPlan(self.config, T, Tc, lib=self._lib, compute_dtype="bf16r" if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")) else "fp32", device=dev,
-                              tuning=self._tuning, mode=mode[:-3] if ig else mode, input_grads=ig, src_of=src_of)
+                              tuning=self._tuning, mode=mode[:-3] if (ig and mode != "decode_ig") else mode, input_grads=ig, src_of=src_of)
             if [(o, n) for o, n, _ in plan.param_info] != [(o, n) for o, n, _ in self._layout]:
                 raise RuntimeError("flat parameter layout of the C plan differs from the module's")
             hit = self._ragged[key] = (plan, _Entry(plan, torch.zeros(plan.workspace_floats, dtype=torch.float32, device=dev)) if ig else None)
@@ -668,11 +700,11 @@ class AE(nn.Module):
             raise ValueError(f"{call}: src_of must be a non-empty list of source indices in [0, {S}) (there are {S} sources), got {list(m)}")
         return m
 
-    def _voices(self, call, emb, N, what):
+    def _voices(self, call, emb, N, what, detach=True):
         C = self._c_emb
         if not torch.is_tensor(emb):
             raise ValueError(f"{call}: emb must be a tensor of shape [{N}, {C}] or [{C}]")
-        e = self._prep(emb.detach()).to(self._flat.device)
+        e = self._prep(emb.detach() if detach else emb).to(self._flat.device)
         if e.dim() == 1 and e.shape[0] == C:
             e = e[None]
         if e.dim() != 2 or e.shape[1] != C or e.shape[0] not in (1, N):
@@ -800,6 +832,40 @@ class AE(nn.Module):
         plan, ws = self._ragged_plan("decode", Tz, (), m)
         plan.forward_latents(self._flat, z, self._c_lat, e, ws)
         return [o.clone() for o in plan.outputs(ws)]
+
+    def decoder_ragged(self, zs, emb):
+        """``decoder`` over latents of DIFFERENT lengths in ONE launch set: zs is a list of [c_lat, Tz_s] tensors, emb is [N, c_emb]
+        (one row per latent) or [c_emb] / [1, c_emb] (one voice for all); returns N tensors [M, T''_j], output j == decoder(zs[j], emb_j),
+        bit-identical to ``decode_ragged(zs, emb)``.
+
+        Differentiable with respect to its inputs: with grad enabled and a latent or ``emb`` that requires grad, the results are views of
+        ONE packed tensor with a ``grad_fn``, and a backward gives every latent leaf a ``.grad`` of its own shape [c_lat, Tz_s] and ``emb``
+        one of its own shape (a single voice gets the sum over the N outputs).  The backward pass of all latents is ONE ragged launch set
+        in fp32 (``RaggedPlan(mode="decode_ig")``); the parameters are frozen on this path (their gradients: ``decoder(z, cond)`` on
+        uniform shapes).  Grad plans have a workspace of their OWN (see ``get_speaker_embeddings_ragged``); a second grad forward of the
+        same lengths while a backward is pending gets a private workspace.  There is no ``src_of`` on the grad path: to render one latent
+        in several voices pass ``[zs[j] for j in src_of]`` -- torch's autograd sums the gradients of a repeated latent.  Under
+        ``compute_dtype: bf16`` the grad path raises: use the uniform ``decoder(z_b, emb_b)``.  Without grad the call is
+        ``decode_ragged(zs, emb)``."""
+        zs = list(zs)
+        need = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in zs + [emb])
+        if not need:
+            return self.decode_ragged(zs, emb)
+        for z in zs:
+            if not torch.is_tensor(z) or z.dim() != 2 or z.shape[0] != self._c_lat:
+                raise ValueError(f"decoder_ragged: every latent must be a [{self._c_lat}, Tz] tensor, got {tuple(z.shape) if torch.is_tensor(z) else type(z)}")
+        if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")):
+            raise RuntimeError("decoder_ragged: input gradients through the ragged path are fp32 only, and compute_dtype is "
+                               f"{self.compute_dtype!r} (ragged plans then run 'bf16r', a forward-only rounding model).  Use the uniform path "
+                               "decoder(z_b, emb_b) per utterance, or detach the inputs")
+        dev = self._flat.device
+        Tz = tuple(int(z.shape[1]) for z in zs)
+        e = self._voices("decoder_ragged", emb, len(zs), "latent", detach=False)
+        z = torch.cat([self._prep(z).to(dev).reshape(-1) for z in zs])   # block s = [c_lat][Tz_s], frames contiguous
+        dec = _RaggedDecoderFunction.apply(self, z, e, Tz)
+        plan = self._ragged_plan("decode_ig", Tz, ())[0]
+        M, base = plan.n_mels, plan.out_off[0]
+        return [dec[o - base:o - base + M * n].view(M, n) for o, n in zip(plan.out_off, plan.out_len)]
 
     def get_speaker_embeddings_ragged(self, x_conds):
         """``get_speaker_embeddings`` (model.py:393-395) over utterances of DIFFERENT lengths in ONE launch set: x_conds is a list of

@@ -367,6 +367,35 @@ int avc_backward_ragged(const avc_plan* p, const float* params, const float* x_c
  * mean[S * c_h] then rstd[S * c_h], row s * c_h + c). */
 int avc_plan_create_ragged_content_grads(const avc_model_cfg* cfg, int S, const int* T, const avc_tuning* tuning, avc_plan** out);
 int avc_content_backward_ragged(const avc_plan* p, const float* params, const float* x, const float* d_muls, float* ws, void* stream);
+/* INPUT GRADIENTS THROUGH THE RAGGED DECODER: avc_plan_create_ragged_decoder_grads(cfg, N, Tz, tuning, out) creates the decoder alone over
+ * N latents of Tz[j] frames, output j from latent j, with a backward pass with respect to its two inputs z and emb.  avc_plan_flags reports
+ * AVC_PLAN_RAGGED | AVC_PLAN_EMB_INPUT | AVC_PLAN_DECODER_ONLY | AVC_PLAN_INPUT_GRADS (no AVC_PLAN_FANOUT: the map is the identity; callers
+ * that decode one latent in several voices index the latents themselves and sum the gradients); avc_plan_ragged_out works; the reflect-pad
+ * rule is the forward plan's (-6).  Its forward runs through avc_decoder_forward_ragged and launches the same kernel instances on the same
+ * operands as the decoder-only plan of avc_plan_create_ragged_fanout with the identity map: ws["dec"] is bit-identical.  On top of that plan
+ * it packs (in the plan's one pack launch) the input-gradient weight images of out_conv, both convs of every block, in_conv and the stacked
+ * AdaIN affine Linears, its InstanceNorm launches store the mean / rstd of every row, and the workspace holds ws["d_cond"], two ping-pong
+ * pairs of gradient rows, ws["d_z"] and ws["d_emb"].  Plans created any other way keep their pack table, workspace and launches.
+ *   avc_decoder_backward_ragged follows an avc_decoder_forward_ragged on the SAME plan, params, z, emb and workspace.  d_dec:
+ * d(loss)/d(dec), fp32, contiguous, packed [M][T''_j] blocks in the order and at the relative offsets avc_plan_ragged_out reports.  z, zc,
+ * emb, seb, sec: the forward's (checked like the forward's; seb = 0 is legal; RESERVED otherwise: the pass reads the weight images, pre-norm
+ * rows, statistics and ws["cond"] the forward left in the workspace).  Results: ws["d_z"], blocks [c_in][Tz_s] at float offset c_in * offz[s]
+ * (offz = prefix sums of Tz), and ws["d_emb"], dense row-major [N][c_cond] whatever seb was (a caller that expanded one voice sums the rows).
+ * Launches, in order: out_conv's input gradient; per block from last to first AdaIN backward of y2 (one wavefront per row at the row's own
+ * length, the activation decision recomputed from the SAVED statistics and ws["cond"]: the forward's, bit for bit; lane 0 stores the row's
+ * d(beta), d(gamma) into ws["d_cond"]; behind an upsampling block the rows are stored as the conv's own [c_h up][T_l] output rows), conv2's
+ * input gradient, AdaIN backward of y1, conv1's input gradient with the nearest-upsampling / identity adjoint of the residual path in its
+ * epilogue join; InstanceNorm backward of the in_conv's rows; the in_conv's input gradient into ws["d_z"]; d(emb) = W_affine^T d(cond), one
+ * uniform input-gradient launch over N columns storing row-major: 1 + 4 n + 3 launches.  One pass writes every element of ws["d_cond"]
+ * exactly once: nothing is zeroed.  fp32 only, parameters frozen, no weight gradients, no atomics, a fixed summation order: two passes give
+ * identical bits.  Every kernel goes to the caller's stream; the calls allocate nothing and synchronise nothing.  -8 with a message naming
+ * the creator on a plan without AVC_PLAN_INPUT_GRADS, on a fan-out plan and when the plan's compute dtype is bf16; -1 on a null argument.
+ * Further named buffers of such a plan (avc_plan_buffer): "dec_y0", "dec_y1_<l>", "dec_y2_<l>" (pre-norm rows, packed [c_h][T] blocks at the
+ * level of the row), "dec_a1_<l>" (the first conv's activations), "dec_st0", "dec_st1_<l>", "dec_st2_<l>" (mean[N * c_h] then rstd[N * c_h],
+ * row j * c_h + c) and "cond" / "d_cond" ([N][2 n 2 c_h]: stage k = 2 l (+ 1 for the second conv) holds beta at 2 k c_h, gamma at (2 k + 1) c_h). */
+int avc_plan_create_ragged_decoder_grads(const avc_model_cfg* cfg, int N, const int* Tz, const avc_tuning* tuning, avc_plan** out);
+int avc_decoder_backward_ragged(const avc_plan* p, const float* params, const float* z, int zc, const float* emb, long seb, long sec,
+                                const float* d_dec, float* ws, void* stream);
 
 /* L1 + KL losses of solver.py:84-86 -> ws["losses"] = {loss_rec, loss_kl}; writes
  * d(lambda_rec*loss_rec)/d(dec) into ws["d_dec"] for avc_backward. */
