@@ -38,6 +38,16 @@ static int fail(int rc, const char* what) {
         if (_rc != 0) return fail(_rc, #expr);     \
     } while (0)
 
+// messages that differ between entry points by the function name only
+static int fail(int rc, const char* fn, const char* what) { return fail(rc, (std::string(fn) + ": " + what).c_str()); }
+// a caller's [rows][cols] matrix with element strides seb / sec (the conv kernel addresses its source with 32-bit element offsets; -1
+// marks a structural zero)
+static int check_row_strides(const char* fn, const char* what, long rows, long cols, long seb, long sec) {
+    if (seb < 0 || sec < 0 || (rows - 1) * seb + (cols - 1) * sec >= (1L << 31))
+        return fail(-1, fn, (std::string(what) + " strides must be non-negative and span less than 2^31 elements").c_str());
+    return 0;
+}
+
 extern "C" const char* avc_last_error(void) { return g_err.c_str(); }
 extern "C" int avc_version(void) { return 100; }
 
@@ -170,6 +180,9 @@ struct avc_plan {
 static bool has_spk(int flags) { return !(flags & (AVC_PLAN_CONTENT_ONLY | AVC_PLAN_DECODER_ONLY)); }
 static bool has_enc(int flags) { return !(flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_DECODER_ONLY)); }
 static bool has_dec(int flags) { return !(flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_CONTENT_ONLY)); }
+// (ragged plans: has_enc / has_dec as above; the speaker encoder stays out wherever the caller brings the embeddings, AVC_PLAN_EMB_INPUT,
+// which every ragged plan with AVC_PLAN_DECODER_ONLY carries)
+static bool rag_has_spk(int flags) { return !(flags & (AVC_PLAN_EMB_INPUT | AVC_PLAN_CONTENT_ONLY)); }
 
 // --------------------------------------------------------------------------
 // plan construction
@@ -276,6 +289,43 @@ static void build_enc_params(avc_plan* p, EncNet& e, const avc_encoder_cfg& c, b
     }
 }
 
+// what every plan asks of the three networks' configurations; prefix: the entry point the message names
+static int check_model_cfg(const avc_model_cfg& cfg, const char* prefix) {
+    if (validate_enc(cfg.spk, true) || validate_enc(cfg.enc, false)) return fail(-2, prefix, "unsupported encoder config");
+    const avc_decoder_cfg& dc = cfg.dec;
+    if (dc.n_conv_blocks < 1 || dc.n_conv_blocks > AVC_MAX_BLOCKS || 2 * dc.n_conv_blocks > 12 || dc.kernel_size < 1 || dc.kernel_size > 8)
+        return fail(-2, prefix, "unsupported decoder config");
+    for (int l = 0; l < dc.n_conv_blocks; ++l)
+        if (dc.upsample[l] != 1 && dc.upsample[l] != 2) return fail(-2, prefix, "upsample must be 1 or 2");
+    if (cfg.spk.c_in != cfg.enc.c_in || cfg.enc.c_in != dc.c_out || dc.c_in != cfg.enc.c_out || dc.c_cond != cfg.spk.c_out)
+        return fail(-2, prefix, "inconsistent channel sizes between the three networks");
+    return 0;
+}
+
+// the decoder's parameters (p->cfg.dec), the tail of the flat buffer: in_conv, the blocks' convs, the 2n affine Linears as one layer, out_conv
+static void build_dec_params(avc_plan* p) {
+    const avc_decoder_cfg& dc = p->cfg.dec;
+    DecNet& d = p->dec;
+    d.c = dc;
+    d.slope = dc.act == 1 ? AVC_LRELU_SLOPE : 0.f;
+    d.n = dc.n_conv_blocks;
+    p->dec_param_off = p->param_floats;
+    d.in_conv = add_layer(p, dc.c_h, dc.c_in, 1, 1, true);
+    for (int l = 0; l < d.n; ++l) d.c1.push_back(add_layer(p, dc.c_h, dc.c_h, dc.kernel_size, 1, true));
+    for (int l = 0; l < d.n; ++l) d.c2.push_back(add_layer(p, dc.c_h * dc.upsample[l], dc.c_h, dc.kernel_size, 1, true));
+    const int a0 = add_layer(p, 2 * dc.c_h, dc.c_cond, 1, 1, false);
+    LayerP& L = p->layers[a0];
+    L.nsrc = 2 * d.n;
+    L.rows = 2 * dc.c_h;
+    L.Cout = 2 * dc.c_h * L.nsrc;
+    for (int i = 1; i < L.nsrc; ++i) {
+        L.w[i] = add_param(p, 2 * dc.c_h, dc.c_cond, 0);
+        L.b[i] = add_param(p, 2 * dc.c_h, 0, 0);
+    }
+    d.affine = a0;
+    d.out_conv = add_layer(p, dc.c_out, dc.c_h, 1, 1, true);
+}
+
 static void plan_init_streams(avc_plan* p);
 
 extern "C" int avc_plan_create(const avc_model_cfg* cfg, int B, int T, int T_cond, avc_plan** out) {
@@ -303,14 +353,8 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
     const bool ig = (flags & AVC_PLAN_INPUT_GRADS) != 0;
     const bool dec_only = (flags & AVC_PLAN_DECODER_ONLY) != 0;
     const bool do_spk = has_spk(flags), do_enc = has_enc(flags), do_dec = has_dec(flags);
-    if (validate_enc(cfg->spk, true) || validate_enc(cfg->enc, false)) return fail(-2, "avc_plan_create: unsupported encoder config");
+    if (int rc = check_model_cfg(*cfg, "avc_plan_create")) return rc;
     const avc_decoder_cfg& dc = cfg->dec;
-    if (dc.n_conv_blocks < 1 || dc.n_conv_blocks > AVC_MAX_BLOCKS || 2 * dc.n_conv_blocks > 12 || dc.kernel_size < 1 || dc.kernel_size > 8)
-        return fail(-2, "avc_plan_create: unsupported decoder config");
-    for (int l = 0; l < dc.n_conv_blocks; ++l)
-        if (dc.upsample[l] != 1 && dc.upsample[l] != 2) return fail(-2, "avc_plan_create: upsample must be 1 or 2");
-    if (cfg->spk.c_in != cfg->enc.c_in || cfg->enc.c_in != dc.c_out || dc.c_in != cfg->enc.c_out || dc.c_cond != cfg->spk.c_out)
-        return fail(-2, "avc_plan_create: inconsistent channel sizes between the three networks");
 
     avc_plan* p = new avc_plan();
     p->cfg = *cfg;
@@ -346,27 +390,8 @@ extern "C" int avc_plan_create_tuned(const avc_model_cfg* cfg, int B, int T, int
     build_enc_params(p, p->spk, cfg->spk, true);
     p->enc_param_off = p->param_floats;
     build_enc_params(p, p->enc, cfg->enc, false);
+    build_dec_params(p);
     DecNet& d = p->dec;
-    d.c = dc;
-    d.slope = dc.act == 1 ? AVC_LRELU_SLOPE : 0.f;
-    d.n = dc.n_conv_blocks;
-    p->dec_param_off = p->param_floats;
-    d.in_conv = add_layer(p, dc.c_h, dc.c_in, 1, 1, true);
-    for (int l = 0; l < d.n; ++l) d.c1.push_back(add_layer(p, dc.c_h, dc.c_h, dc.kernel_size, 1, true));
-    for (int l = 0; l < d.n; ++l) d.c2.push_back(add_layer(p, dc.c_h * dc.upsample[l], dc.c_h, dc.kernel_size, 1, true));
-    {
-        int a0 = add_layer(p, 2 * dc.c_h, dc.c_cond, 1, 1, false);
-        LayerP& L = p->layers[a0];
-        L.nsrc = 2 * d.n;
-        L.rows = 2 * dc.c_h;
-        L.Cout = 2 * dc.c_h * L.nsrc;
-        for (int i = 1; i < L.nsrc; ++i) {
-            L.w[i] = add_param(p, 2 * dc.c_h, dc.c_cond, 0);
-            L.b[i] = add_param(p, 2 * dc.c_h, 0, 0);
-        }
-        d.affine = a0;
-    }
-    d.out_conv = add_layer(p, dc.c_out, dc.c_h, 1, 1, true);
 
     // ---- time schedules + reflect-pad validity (reference raises the same way)
     auto sched_enc = [&](EncNet& e, int T0) -> int {
@@ -971,6 +996,29 @@ static void set_res(ConvArgs& a, const float* res, int mode, long rb, long rc, i
     a.rb = rb; a.rc = rc; a.rt = rt; a.Tres = Tres;
 }
 
+// The speaker encoder's dense stack (dense blocks + output layer) as the ONE fused launch of dense.hip reads it: the forward images and
+// biases, or (backward; params may be NULL) the input-gradient images.  No side effects.  Callers add the ends of their pass: in, emb and
+// the blocks' out2 (forward); in, dpooled and the layers' dz (backward).
+static DenseArgs dense_stack_args(const avc_plan* p, const EncNet& e, const float* params, float* ws, bool backward) {
+    DenseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nlayers = 2 * e.nd + 1;
+    a.B = p->B; a.C = e.c.c_h; a.slope = e.slope;
+    for (int l = 0; l < a.nlayers; ++l) {
+        const bool last = (l == a.nlayers - 1);
+        const LayerP& L = p->layers[last ? e.outl : ((l & 1) ? e.dn2[l / 2] : e.dn1[l / 2])];
+        DenseLayer& D = a.layer[l];
+        D.wp = ws + (backward ? L.wpd : L.wpf);
+        if (!backward) D.bias = p->par(params, L.b[0]);
+        D.Cin = L.Cin; D.Cout = L.Cout; D.Mp = backward ? L.Mp_d : L.Mp_f;
+        D.Kp = backward ? L.nchunk_d * L.CKd : L.nchunk_f * L.CK;
+        if (!last) D.act = ws + ((l & 1) ? e.d2[l / 2] : e.d1[l / 2]);
+        a.Kmax = D.Kp > a.Kmax ? D.Kp : a.Kmax;
+        a.Wmax = D.Kp * D.Mp > a.Wmax ? D.Kp * D.Mp : a.Wmax;
+    }
+    return a;
+}
+
 struct BwdCtx {
     const avc_plan* p;
     const float* params;
@@ -1284,26 +1332,10 @@ static int forward_impl(const avc_plan* p, const float* params, const float* x, 
         else RUN(avc_launch_timepool_fwd(ws + e.out[e.n], B, Cc, Tn, ws + e.pooled, s));
         // dense blocks + output layer: ONE fused launch (dense.hip); activations channel-major [C][B]
         {
-            DenseArgs da;
-            memset(&da, 0, sizeof(da));
-            da.nlayers = 2 * e.nd + 1;
-            da.B = B; da.C = Cc; da.slope = SL;
+            DenseArgs da = dense_stack_args(p, e, params, ws, false);
             da.in = ws + e.hd[0];
             da.emb = ws + p->emb;
-            for (int l = 0; l < da.nlayers; ++l) {
-                const bool last = (l == da.nlayers - 1);
-                const LayerP& L = p->layers[last ? e.outl : ((l & 1) ? e.dn2[l / 2] : e.dn1[l / 2])];
-                DenseLayer& D = da.layer[l];
-                D.wp = ws + L.wpf;
-                D.bias = p->par(params, L.b[0]);
-                D.Cin = L.Cin; D.Cout = L.Cout; D.Kp = L.nchunk_f * L.CK; D.Mp = L.Mp_f;
-                if (!last) {
-                    D.act = ws + ((l & 1) ? e.d2[l / 2] : e.d1[l / 2]);
-                    D.out2 = (l & 1) ? ws + e.hd[l / 2 + 1] : nullptr;
-                }
-                da.Kmax = D.Kp > da.Kmax ? D.Kp : da.Kmax;
-                da.Wmax = D.Kp * D.Mp > da.Wmax ? D.Kp * D.Mp : da.Wmax;
-            }
+            for (int l = 0; l < e.nd; ++l) da.layer[2 * l + 1].out2 = ws + e.hd[l + 1];   // (the second Linear of a block also stores h_{l+1})
             RUN(avc_launch_dense(da, 0, s));
         }
     }
@@ -1823,27 +1855,14 @@ int avc_backward_impl(const avc_plan* p, const float* params, const float* x, lo
         // output layer + dense blocks: ONE fused dgrad launch produces every dz (and d pooled);
         // the weight gradients are ordinary GEMMs over the batch on the wgrad stream
         {
-            DenseArgs da;
-            memset(&da, 0, sizeof(da));
-            da.nlayers = 2 * e.nd + 1;
-            da.B = B; da.C = Cc; da.slope = SL;
-            da.in = ws + p->demb;      // [c_out][B] channel-major
-            da.in2 = nullptr;           // (upstream d_emb is already folded into demb above)
+            DenseArgs da = dense_stack_args(p, e, nullptr, ws, true);
+            da.in = ws + p->demb;      // [c_out][B] channel-major (upstream d_emb is already folded into demb above: no in2)
             da.dpooled = dhA;
             float* dzl[AVC_DENSE_MAXL];
             for (int l = 0; l < da.nlayers; ++l) {
                 const bool last = (l == da.nlayers - 1);
-                const LayerP& L = p->layers[last ? e.outl : ((l & 1) ? e.dn2[l / 2] : e.dn1[l / 2])];
-                DenseLayer& D = da.layer[l];
-                D.wp = ws + L.wpd;
-                D.Cin = L.Cin; D.Cout = L.Cout; D.Kp = L.nchunk_d * L.CKd; D.Mp = L.Mp_d;
                 dzl[l] = last ? nullptr : c.fresh((long)Cc * B);
-                if (!last) {
-                    D.act = ws + ((l & 1) ? e.d2[l / 2] : e.d1[l / 2]);
-                    D.dz = dzl[l];
-                }
-                da.Kmax = D.Kp > da.Kmax ? D.Kp : da.Kmax;
-                da.Wmax = D.Kp * D.Mp > da.Wmax ? D.Kp * D.Mp : da.Wmax;
+                da.layer[l].dz = dzl[l];
             }
             if (!dry) RUN(avc_launch_dense(da, 1, s));
             if (!dry) avc_prof_mark(1, s);
@@ -2015,6 +2034,33 @@ static void rag_level(avc_plan* p, avc_plan::RagLevel& L, const std::vector<int>
     L.dtile = rag_put(p, tiles);
 }
 
+// Workspace of the ragged plans with a backward pass (AVC_PLAN_INPUT_GRADS).  The order of the allocations is the workspace layout.
+// one branch, one stream, no weight gradient: two ping-pong pairs of gradient rows suffice
+static void rag_alloc_grad_rows(avc_plan* p, long floats) {
+    p->gA2 = p->alloc(floats);   // G_l: d(loss)/d(out_l), the residual path's gradient
+    p->gC2 = p->alloc(floats);
+    p->gA = p->alloc(floats);    // the gradients entering conv2 / conv1 of a block: masked (speaker), or what an InstanceNorm backward leaves
+    p->gB = p->alloc(floats);
+}
+// row statistics of every InstanceNorm of an encoder / the decoder: mean[n * C] | rstd[n * C], row b * C + c
+template <class Net>
+static void rag_alloc_stats(avc_plan* p, Net& net, long n, long C) {
+    net.st0 = p->alloc(2 * n * C);
+    for (int l = 0; l < net.n; ++l) {
+        net.st1[l] = p->alloc(2 * n * C);
+        net.st2[l] = p->alloc(2 * n * C);
+    }
+}
+static void rag_alloc_enc_input_grads(avc_plan* p, EncNet& e, long sumT) {
+    e.dcat = p->alloc((long)e.CC * sumT);
+    e.dx = p->alloc((long)e.c.c_in * sumT);
+}
+// named["<prefix>_<name>_<l>"] for every level l of every listed per-level buffer
+static void rag_name_levels(avc_plan* p, const std::string& prefix, int n, std::initializer_list<std::pair<const char*, const long*>> bufs) {
+    for (int l = 0; l < n; ++l)
+        for (const auto& b : bufs) p->named[prefix + "_" + b.first + "_" + std::to_string(l)] = b.second[l];
+}
+
 static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, int flags, int N, const int* src_of,
                            const avc_tuning* tuning, avc_plan** out);
 
@@ -2079,21 +2125,14 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
                            const avc_tuning* tuning, avc_plan** out) {
     const bool ig = (flags & AVC_PLAN_INPUT_GRADS) != 0;
     const bool fan = (flags & AVC_PLAN_FANOUT) != 0;
-    const bool do_spk = !(flags & (AVC_PLAN_EMB_INPUT | AVC_PLAN_CONTENT_ONLY)), do_enc = !(flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_DECODER_ONLY)),
-               do_dec = !(flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_CONTENT_ONLY));
+    const bool do_spk = rag_has_spk(flags), do_enc = has_enc(flags), do_dec = has_dec(flags);
     const int Nd = do_dec ? (fan ? N : B) : 0;   // the decoder's sample count
     if (!do_enc && !do_dec) T = T_cond;   // (speaker-only: T is ignored; the shared length checks below then read T_cond twice)
     if (!cfg || !out || !T || B < 1) return fail(-1, "avc_plan_create_ragged: bad arguments");
     if (tuning && tuning->struct_size != (int)sizeof(avc_tuning)) return fail(-1, "avc_plan_create_ragged: avc_tuning of another library version (use avc_tuning_init)");
     if (!T_cond || !do_spk) T_cond = T;
-    if (validate_enc(cfg->spk, true) || validate_enc(cfg->enc, false)) return fail(-2, "avc_plan_create_ragged: unsupported encoder config");
+    if (int rc = check_model_cfg(*cfg, "avc_plan_create_ragged")) return rc;
     const avc_decoder_cfg& dc = cfg->dec;
-    if (dc.n_conv_blocks < 1 || dc.n_conv_blocks > AVC_MAX_BLOCKS || 2 * dc.n_conv_blocks > 12 || dc.kernel_size < 1 || dc.kernel_size > 8)
-        return fail(-2, "avc_plan_create_ragged: unsupported decoder config");
-    for (int l = 0; l < dc.n_conv_blocks; ++l)
-        if (dc.upsample[l] != 1 && dc.upsample[l] != 2) return fail(-2, "avc_plan_create_ragged: upsample must be 1 or 2");
-    if (cfg->spk.c_in != cfg->enc.c_in || cfg->enc.c_in != dc.c_out || dc.c_in != cfg->enc.c_out || dc.c_cond != cfg->spk.c_out)
-        return fail(-2, "avc_plan_create_ragged: inconsistent channel sizes between the three networks");
 
     avc_plan* p = new avc_plan();
     p->cfg = *cfg;
@@ -2114,27 +2153,8 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
     build_enc_params(p, p->spk, cfg->spk, true);
     p->enc_param_off = p->param_floats;
     build_enc_params(p, p->enc, cfg->enc, false);
+    build_dec_params(p);
     DecNet& d = p->dec;
-    d.c = dc;
-    d.slope = dc.act == 1 ? AVC_LRELU_SLOPE : 0.f;
-    d.n = dc.n_conv_blocks;
-    p->dec_param_off = p->param_floats;
-    d.in_conv = add_layer(p, dc.c_h, dc.c_in, 1, 1, true);
-    for (int l = 0; l < d.n; ++l) d.c1.push_back(add_layer(p, dc.c_h, dc.c_h, dc.kernel_size, 1, true));
-    for (int l = 0; l < d.n; ++l) d.c2.push_back(add_layer(p, dc.c_h * dc.upsample[l], dc.c_h, dc.kernel_size, 1, true));
-    {
-        int a0 = add_layer(p, 2 * dc.c_h, dc.c_cond, 1, 1, false);
-        LayerP& L = p->layers[a0];
-        L.nsrc = 2 * d.n;
-        L.rows = 2 * dc.c_h;
-        L.Cout = 2 * dc.c_h * L.nsrc;
-        for (int i = 1; i < L.nsrc; ++i) {
-            L.w[i] = add_param(p, 2 * dc.c_h, dc.c_cond, 0);
-            L.b[i] = add_param(p, 2 * dc.c_h, 0, 0);
-        }
-        d.affine = a0;
-    }
-    d.out_conv = add_layer(p, dc.c_out, dc.c_h, 1, 1, true);
 
     // ---- per-sample time schedules; the reference's reflect-pad rule per utterance
     auto sched = [&](EncNet& e, const int* T0, std::vector<avc_plan::RagLevel>& lv) -> int {
@@ -2266,15 +2286,11 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
         p->emb = p->alloc(Bl * dc.c_cond);
         p->named["emb"] = p->emb;
     }
-    if (ig && do_spk) {   // gradient temporaries of avc_backward_ragged (one branch, one stream, no weight gradient: two ping-pong pairs suffice)
+    if (ig && do_spk) {   // avc_backward_ragged: d(cat), d(x_cond), the gradient rows, the dense stack's temporaries
         EncNet& e = p->spk;
         const long C = e.c.c_h, sumT = p->rl_spk[0].off[B];
-        e.dcat = p->alloc((long)e.CC * sumT);
-        e.dx = p->alloc((long)e.c.c_in * sumT);
-        p->gA2 = p->alloc(C * sumT);    // G_l: d(loss)/d(out_l), the residual path's gradient
-        p->gC2 = p->alloc(C * sumT);
-        p->gA = p->alloc(C * sumT);     // masked gradients entering conv2 / conv1 of a block
-        p->gB = p->alloc(C * sumT);
+        rag_alloc_enc_input_grads(p, e, sumT);
+        rag_alloc_grad_rows(p, C * sumT);
         p->demb = p->alloc(Bl * dc.c_cond);
         p->dhA = p->alloc(C * Bl);
         p->dz = p->alloc(C * Bl);       // the dense stack's d(pre-activation) rows: written by its backward kernel, read by nobody (no weight gradient)
@@ -2282,14 +2298,8 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
         // the saved activations the backward pass masks by (tests read the ReLU branch the engine took from them)
         p->named["spk_cat"] = e.cat;
         p->named["spk_h0"] = e.h0;
-        for (int l = 0; l < e.n; ++l) {
-            p->named["spk_a1_" + std::to_string(l)] = e.a1[l];
-            p->named["spk_a2_" + std::to_string(l)] = e.a2[l];
-        }
-        for (int l = 0; l < e.nd; ++l) {
-            p->named["spk_d1_" + std::to_string(l)] = e.d1[l];
-            p->named["spk_d2_" + std::to_string(l)] = e.d2[l];
-        }
+        rag_name_levels(p, "spk", e.n, {{"a1", e.a1}, {"a2", e.a2}});
+        rag_name_levels(p, "spk", e.nd, {{"d1", e.d1}, {"d2", e.d2}});
     }
     if (do_enc) {
         alloc_enc(p->enc, p->rl_enc, false);
@@ -2299,28 +2309,15 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
     if (ig && do_enc) {   // avc_content_backward_ragged: row statistics of every InstanceNorm, d(cat), d(x), two ping-pong pairs of gradient rows
         EncNet& e = p->enc;
         const long C = e.c.c_h, sumT = p->rl_enc[0].off[B];
-        e.st0 = p->alloc(2 * Bl * C);   // mean[B * C] | rstd[B * C], row b * C + c
-        for (int l = 0; l < e.n; ++l) {
-            e.st1[l] = p->alloc(2 * Bl * C);
-            e.st2[l] = p->alloc(2 * Bl * C);
-        }
-        e.dcat = p->alloc((long)e.CC * sumT);
-        e.dx = p->alloc((long)e.c.c_in * sumT);
-        p->gA2 = p->alloc(C * sumT);    // G_l: d(loss)/d(out_l), the residual path's gradient
-        p->gC2 = p->alloc(C * sumT);
-        p->gA = p->alloc(C * sumT);     // d(y): what an InstanceNorm backward leaves for the conv's input gradient
-        p->gB = p->alloc(C * sumT);     // d(a1): conv2's input gradient
+        rag_alloc_stats(p, e, Bl, C);
+        rag_alloc_enc_input_grads(p, e, sumT);
+        rag_alloc_grad_rows(p, C * sumT);
         p->named["d_x"] = e.dx;
         // what the backward pass masks by (tests read the ReLU branch the engine took: cat > 0, saved y > saved row mean)
         p->named["enc_cat"] = e.cat;
         p->named["enc_y0"] = e.h0;
         p->named["enc_st0"] = e.st0;
-        for (int l = 0; l < e.n; ++l) {
-            p->named["enc_y1_" + std::to_string(l)] = e.y1[l];
-            p->named["enc_y2_" + std::to_string(l)] = e.y2[l];
-            p->named["enc_st1_" + std::to_string(l)] = e.st1[l];
-            p->named["enc_st2_" + std::to_string(l)] = e.st2[l];
-        }
+        rag_name_levels(p, "enc", e.n, {{"y1", e.y1}, {"y2", e.y2}, {"st1", e.st1}, {"st2", e.st2}});
     }
     if (do_dec) {   // the in_conv stage lives on the B sources' level, everything above on the Nd outputs' levels
         d.cond = p->alloc((long)Nd * 2 * d.n * 2 * Cd);
@@ -2338,16 +2335,9 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
     }
     if (ig && do_dec) {   // avc_decoder_backward_ragged: row statistics of every InstanceNorm, d(cond), two ping-pong pairs of gradient rows, d(z), d(emb)
         const long Nl = Nd, top = p->rl_dec[d.n].off[Nd];   // (the last level is the longest: upsample factors are 1 or 2)
-        d.st0 = p->alloc(2 * Nl * Cd);   // mean[N * C] | rstd[N * C], row b * C + c
-        for (int l = 0; l < d.n; ++l) {
-            d.st1[l] = p->alloc(2 * Nl * Cd);
-            d.st2[l] = p->alloc(2 * Nl * Cd);
-        }
+        rag_alloc_stats(p, d, Nl, Cd);
         d.dcond = p->alloc(Nl * 2 * d.n * 2 * Cd);
-        p->gA2 = p->alloc(Cd * top);    // G_l: d(loss)/d(out_l), the residual path's gradient
-        p->gC2 = p->alloc(Cd * top);
-        p->gA = p->alloc(Cd * top);     // d(y): what an AdaIN backward leaves for the conv's input gradient
-        p->gB = p->alloc(Cd * top);     // d(a1): conv2's input gradient
+        rag_alloc_grad_rows(p, Cd * top);
         p->dz = p->alloc(Cz * lz->off[B]);
         p->demb_rm = p->alloc(Nl * dc.c_cond);
         p->named["d_z"] = p->dz;
@@ -2356,13 +2346,7 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
         // what the backward pass masks by (tests read the activation branch the engine took from the saved rows and statistics)
         p->named["dec_y0"] = d.y0;
         p->named["dec_st0"] = d.st0;
-        for (int l = 0; l < d.n; ++l) {
-            p->named["dec_y1_" + std::to_string(l)] = d.y1[l];
-            p->named["dec_a1_" + std::to_string(l)] = d.a1[l];
-            p->named["dec_y2_" + std::to_string(l)] = d.y2[l];
-            p->named["dec_st1_" + std::to_string(l)] = d.st1[l];
-            p->named["dec_st2_" + std::to_string(l)] = d.st2[l];
-        }
+        rag_name_levels(p, "dec", d.n, {{"y1", d.y1}, {"a1", d.a1}, {"y2", d.y2}, {"st1", d.st1}, {"st2", d.st2}});
     }
     p->rag_tab = p->alloc((long)p->rag_host.size());
     plan_init_streams(p);
@@ -2468,8 +2452,7 @@ static int rag_enc_front(const avc_plan* p, const EncNet& e, const std::vector<a
 // z != NULL (decoder-only fan-out plans): the decoder's in_conv reads the caller's latent blocks of zc channels in place of ws["muls"].
 static int rag_forward_impl(const avc_plan* p, const float* params, const float* x, const float* x_cond, const float* emb, long seb, long sec,
                             const float* z, int zc, float* ws, hipStream_t s) {
-    const bool do_spk = !(p->flags & (AVC_PLAN_EMB_INPUT | AVC_PLAN_CONTENT_ONLY)), do_enc = !(p->flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_DECODER_ONLY)),
-               do_dec = !(p->flags & (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_CONTENT_ONLY));
+    const bool do_spk = rag_has_spk(p->flags), do_enc = has_enc(p->flags), do_dec = has_dec(p->flags);
     const int B = p->B;
     // tables -> workspace (a few KB; stream-ordered in front of everything that reads them)
     RUN((int)hipMemcpyAsync(ws + p->rag_tab, p->rag_host.data(), p->rag_host.size() * sizeof(int), hipMemcpyHostToDevice, s));
@@ -2515,26 +2498,10 @@ static int rag_forward_impl(const avc_plan* p, const float* params, const float*
             RUN(avc_launch_conv(b, s, 0, p->tun));
         }
         RUN(avc_launch_rag_timepool_fwd(ws + e.out[e.n], tab + lv[e.n].dT, tab + lv[e.n].doff, B, C, ws + e.pooled, s));
-        DenseArgs da;
-        memset(&da, 0, sizeof(da));
-        da.nlayers = 2 * e.nd + 1;
-        da.B = B; da.C = C; da.slope = SL;
+        DenseArgs da = dense_stack_args(p, e, params, ws, false);
         da.in = ws + e.hd[0];
         da.emb = ws + p->emb;
-        for (int l = 0; l < da.nlayers; ++l) {
-            const bool last = (l == da.nlayers - 1);
-            const LayerP& L = p->layers[last ? e.outl : ((l & 1) ? e.dn2[l / 2] : e.dn1[l / 2])];
-            DenseLayer& D = da.layer[l];
-            D.wp = ws + L.wpf;
-            D.bias = p->par(params, L.b[0]);
-            D.Cin = L.Cin; D.Cout = L.Cout; D.Kp = L.nchunk_f * L.CK; D.Mp = L.Mp_f;
-            if (!last) {
-                D.act = ws + ((l & 1) ? e.d2[l / 2] : e.d1[l / 2]);
-                D.out2 = (l & 1) ? ws + e.hd[l / 2 + 1] : nullptr;
-            }
-            da.Kmax = D.Kp > da.Kmax ? D.Kp : da.Kmax;
-            da.Wmax = D.Kp * D.Mp > da.Wmax ? D.Kp * D.Mp : da.Wmax;
-        }
+        for (int l = 0; l < e.nd; ++l) da.layer[2 * l + 1].out2 = ws + e.hd[l + 1];
         RUN(avc_launch_dense(da, 0, s));
     }
     if (do_enc) {   // ---------------- content encoder on the source utterances (model.py:301-323)
@@ -2634,9 +2601,7 @@ extern "C" int avc_forward_ragged_emb(const avc_plan* p, const float* params, co
     if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_EMB_INPUT))
         return fail(-8, "avc_forward_ragged_emb: the plan was not created by avc_plan_create_ragged_ex with AVC_PLAN_EMB_INPUT");
     if (!emb) return fail(-1, "avc_forward_ragged_emb: emb is NULL (the plan has no speaker encoder to compute it)");
-    // (the conv kernel addresses its source with 32-bit element offsets; -1 marks a structural zero)
-    if (seb < 0 || sec < 0 || (p->Nd - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
-        return fail(-1, "avc_forward_ragged_emb: emb strides must be non-negative and span less than 2^31 elements");
+    if (int rc = check_row_strides("avc_forward_ragged_emb", "emb", p->Nd, p->cfg.dec.c_cond, seb, sec)) return rc;
     return rag_forward_impl(p, params, x, nullptr, emb, seb, sec, nullptr, 0, ws, (hipStream_t)stream);
 }
 
@@ -2654,9 +2619,76 @@ extern "C" int avc_decoder_forward_ragged(const avc_plan* p, const float* params
     if (!emb) return fail(-1, "avc_decoder_forward_ragged: emb is NULL (the plan has no speaker encoder to compute it)");
     if (zc < p->cfg.dec.c_in)
         return fail(-1, "avc_decoder_forward_ragged: zc is too small: a latent block has at least c_in rows (c_in: mu alone, 2 c_out: ws[\"muls\"] blocks)");
-    if (seb < 0 || sec < 0 || (p->Nd - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
-        return fail(-1, "avc_decoder_forward_ragged: emb strides must be non-negative and span less than 2^31 elements");
+    if (int rc = check_row_strides("avc_decoder_forward_ragged", "emb", p->Nd, p->cfg.dec.c_cond, seb, sec)) return rc;
     return rag_forward_impl(p, params, nullptr, nullptr, emb, seb, sec, z, zc, ws, (hipStream_t)stream);
+}
+
+// What the ragged backward passes share: where they run, and the plan's two ping-pong pairs of gradient rows.
+struct RagBwd {
+    const avc_plan* p;
+    float* ws;
+    const int* tab;
+    hipStream_t s;
+    float slope;
+    float *gA, *gC;     // G_l = d(loss)/d(out_l), the residual path's gradient, and its next value
+    float *dyA, *dyB;   // the rows entering a block's two input-gradient launches
+    RagBwd(const avc_plan* p_, float* ws_, hipStream_t s_, float slope_)
+        : p(p_), ws(ws_), tab((const int*)(ws_ + p_->rag_tab)), s(s_), slope(slope_), gA(ws_ + p_->gA2), gC(ws_ + p_->gC2), dyA(ws_ + p_->gA),
+          dyB(ws_ + p_->gB) {}
+    int launch(const ConvArgs& a) const { return avc_launch_conv(a, s, 11, p->tun); }
+};
+
+// An input-gradient launch on packed rows: dy of level `sl` -> dx of level `ol` (tiles run over `ol`)
+// (always the 64 x 64 tile: a ragged tile is one sample's 64 frames, the mirrored instances exist on that tile only)
+static ConvArgs rag_dgrad(const RagBwd& c, const LayerP& L, const float* dy, const avc_plan::RagLevel& sl, int cx, float* dx,
+                          const avc_plan::RagLevel& ol, int cout) {
+    ConvArgs a = mk_dgrad(c.slope, L, c.ws, dy, 0, -1, 1, 1, 1, 0, 64, dx, 0, 0, 1);
+    set_rag(a, c.tab, sl, cx, ol, ol, cout);
+    return a;
+}
+
+// InstanceNorm backward over the n samples' [C][T_b] rows of level l: g -> dy, from the saved rows at y and their statistics at st.
+// coff >= 0: AdaIN with the decoder's cond slice at coff (its d(cond) slice is written too); up: planar store factor.  coff < 0: plain.
+static int rag_in_bwd(const RagBwd& c, int n, int C, const float* g, long y, long st, const avc_plan::RagLevel& l, float* dy, int coff = -1,
+                      int up = 1) {
+    const DecNet& d = c.p->dec;
+    RagINBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g = g; a.y = c.ws + y; a.mean = c.ws + st; a.rstd = c.ws + st + (long)n * C; a.dy = dy;
+    a.T = c.tab + l.dT; a.off = c.tab + l.doff;
+    a.B = n; a.C = C; a.slope = c.slope;
+    if (coff >= 0) { a.cond = c.ws + d.cond; a.dcond = c.ws + d.dcond; a.cond_sb = (long)2 * d.n * 2 * C; a.cond_off = coff; a.up = up; }
+    return avc_launch_rag_in_bwd(a, c.s);
+}
+
+// The end of an encoder's input gradient, from dy = d(loss)/d(in_conv's output):
+//   d(cat) for the bank channels, masked by the bank's activations (cat > 0), then
+//   d(x) = W_in[:, nb c_bank:]^T dy + sum_g pad_g^T(bank_g^T(dcat_g)): nb + 1 launches, each after the first adds the running sum through
+//   its residual join, in place -- a fixed order.  Stored as [T_b][M] rows, x's own layout, at e.dx.
+static int rag_enc_input_tail(const RagBwd& c, const EncNet& e, const avc_plan::RagLevel& l0, const float* dy) {
+    const avc_plan* p = c.p;
+    const int C = e.c.c_h, M = e.c.c_in;
+    {
+        ConvArgs a = rag_dgrad(c, p->layers[e.in_conv], dy, l0, C, nullptr, l0, e.CC);
+        a.g[0].out2 = c.ws + e.dcat;
+        a.g[0].mask = c.ws + e.cat;
+        RUN(c.launch(a));
+    }
+    float* dx = c.ws + e.dx;
+    {
+        ConvArgs a = rag_dgrad(c, p->layers[e.in_pass], dy, l0, C, dx, l0, M);
+        a.oc = 1; a.ot = M;
+        RUN(c.launch(a));
+    }
+    for (int g = 0; g < e.nb; ++g) {
+        ConvArgs a = rag_dgrad(c, p->layers[e.bank[g]], c.ws + e.dcat, l0, e.CC, dx, l0, M);
+        a.rag.xc0 = g * e.c.c_bank;
+        a.oc = 1; a.ot = M;
+        set_rag_res(a, c.tab, dx, AVC_RES_IDENTITY, l0, M);
+        a.rc = 1; a.rt = M;
+        RUN(c.launch(a));
+    }
+    return 0;
 }
 
 // The backward pass of a ragged speaker plan with AVC_PLAN_INPUT_GRADS: d(loss)/d(x_cond) from d(loss)/d(emb), parameters frozen.
@@ -2668,86 +2700,38 @@ extern "C" int avc_decoder_forward_ragged(const avc_plan* p, const float* params
 static int rag_backward_impl(const avc_plan* p, const float* d_emb, long seb, long sec, float* ws, hipStream_t s) {
     const int B = p->B;
     const EncNet& e = p->spk;
-    const float SL = e.slope;
     const std::vector<avc_plan::RagLevel>& lv = p->rl_spk;
-    const int C = e.c.c_h, M = e.c.c_in;
-    const int* tab = (const int*)(ws + p->rag_tab);
+    const int C = e.c.c_h;
+    RagBwd c(p, ws, s, e.slope);
+    const int* tab = c.tab;
     RUN(avc_launch_transpose_strided(ws + p->demb, d_emb, seb, sec, B, e.c.c_out, s));
     float* dhA = ws + p->dhA;
     {
-        DenseArgs da;
-        memset(&da, 0, sizeof(da));
-        da.nlayers = 2 * e.nd + 1;
-        da.B = B; da.C = C; da.slope = SL;
+        DenseArgs da = dense_stack_args(p, e, nullptr, ws, true);
         da.in = ws + p->demb;
         da.dpooled = dhA;
-        for (int l = 0; l < da.nlayers; ++l) {
-            const bool last = (l == da.nlayers - 1);
-            const LayerP& L = p->layers[last ? e.outl : ((l & 1) ? e.dn2[l / 2] : e.dn1[l / 2])];
-            DenseLayer& D = da.layer[l];
-            D.wp = ws + L.wpd;
-            D.Cin = L.Cin; D.Cout = L.Cout; D.Kp = L.nchunk_d * L.CKd; D.Mp = L.Mp_d;
-            if (!last) {
-                D.act = ws + ((l & 1) ? e.d2[l / 2] : e.d1[l / 2]);
-                D.dz = ws + p->dz;
-            }
-            da.Kmax = D.Kp > da.Kmax ? D.Kp : da.Kmax;
-            da.Wmax = D.Kp * D.Mp > da.Wmax ? D.Kp * D.Mp : da.Wmax;
-        }
+        for (int l = 0; l < da.nlayers - 1; ++l) da.layer[l].dz = ws + p->dz;
         RUN(avc_launch_dense(da, 1, s));
     }
-    float* gA = ws + p->gA2;
-    float* gC = ws + p->gC2;
-    float* dyA = ws + p->gA;
-    float* dyB = ws + p->gB;
-    // An input-gradient launch on packed rows: dy of level `sl` -> dx of level `ol` (tiles run over `ol`)
-    // (every launch below asks for the 64 x 64 tile: a ragged tile is one sample's 64 frames, the mirrored instances exist on that tile only)
-    auto dgrad = [&](const LayerP& L, const float* dy, const avc_plan::RagLevel& sl, int cx, float* dx, const avc_plan::RagLevel& ol, int cout) {
-        ConvArgs a = mk_dgrad(SL, L, ws, dy, 0, -1, 1, 1, 1, 0, 64, dx, 0, 0, 1);
-        set_rag(a, tab, sl, cx, ol, ol, cout);
-        return a;
-    };
-    RUN(avc_launch_rag_timepool_bwd(dhA, ws + e.a2[e.n - 1], tab + lv[e.n].dT, tab + lv[e.n].doff, B, C, lv[e.n].off[B], gA, dyA, SL, s));
+    RUN(avc_launch_rag_timepool_bwd(dhA, ws + e.a2[e.n - 1], tab + lv[e.n].dT, tab + lv[e.n].doff, B, C, lv[e.n].off[B], c.gA, c.dyA, c.slope, s));
     for (int l = e.n - 1; l >= 0; --l) {
         const int sub = e.c.subsample[l];
         {   // dyB = conv2^T(dyA) masked by a1
-            ConvArgs a = dgrad(p->layers[e.c2[l]], dyA, lv[l + 1], C, nullptr, lv[l], C);
-            a.g[0].out2 = dyB;
+            ConvArgs a = rag_dgrad(c, p->layers[e.c2[l]], c.dyA, lv[l + 1], C, nullptr, lv[l], C);
+            a.g[0].out2 = c.dyB;
             a.g[0].mask = ws + e.a1[l];
-            RUN(avc_launch_conv(a, s, 11, p->tun));
+            RUN(c.launch(a));
         }
         {   // G_l = conv1^T(dyB) + pool^T(G_{l+1}); dyA = G_l masked by the activation that produced out_l
-            ConvArgs a = dgrad(p->layers[e.c1[l]], dyB, lv[l], C, l > 0 ? gC : nullptr, lv[l], C);
-            set_rag_res(a, tab, gA, sub > 1 ? AVC_RES_POOLT : AVC_RES_IDENTITY, lv[l + 1], C);
-            a.g[0].out2 = dyA;
+            ConvArgs a = rag_dgrad(c, p->layers[e.c1[l]], c.dyB, lv[l], C, l > 0 ? c.gC : nullptr, lv[l], C);
+            set_rag_res(a, tab, c.gA, sub > 1 ? AVC_RES_POOLT : AVC_RES_IDENTITY, lv[l + 1], C);
+            a.g[0].out2 = c.dyA;
             a.g[0].mask = (l > 0) ? ws + e.a2[l - 1] : ws + e.h0;
-            RUN(avc_launch_conv(a, s, 11, p->tun));
+            RUN(c.launch(a));
         }
-        float* t = gA; gA = gC; gC = t;
+        std::swap(c.gA, c.gC);
     }
-    {   // d(cat) for the bank channels, masked by the bank's activations (cat > 0)
-        ConvArgs a = dgrad(p->layers[e.in_conv], dyA, lv[0], C, nullptr, lv[0], e.CC);
-        a.g[0].out2 = ws + e.dcat;
-        a.g[0].mask = ws + e.cat;
-        RUN(avc_launch_conv(a, s, 11, p->tun));
-    }
-    // d(x_cond) = W_in[:, nb c_bank:]^T dy_in + sum_g pad_g^T(bank_g^T(dcat_g)): nb + 1 launches, each after the first adds the running sum
-    // through its residual join, in place -- a fixed order.  Stored as [T_b][M] rows: x_cond's own layout.
-    float* dx = ws + e.dx;
-    {
-        ConvArgs a = dgrad(p->layers[e.in_pass], dyA, lv[0], C, dx, lv[0], M);
-        a.oc = 1; a.ot = M;
-        RUN(avc_launch_conv(a, s, 11, p->tun));
-    }
-    for (int g = 0; g < e.nb; ++g) {
-        ConvArgs a = dgrad(p->layers[e.bank[g]], ws + e.dcat, lv[0], e.CC, dx, lv[0], M);
-        a.rag.xc0 = g * e.c.c_bank;
-        a.oc = 1; a.ot = M;
-        set_rag_res(a, tab, dx, AVC_RES_IDENTITY, lv[0], M);
-        a.rc = 1; a.rt = M;
-        RUN(avc_launch_conv(a, s, 11, p->tun));
-    }
-    return 0;
+    return rag_enc_input_tail(c, e, lv[0], c.dyA);
 }
 
 extern "C" int avc_backward_ragged(const avc_plan* p, const float* params, const float* x_cond, const float* d_emb, long seb, long sec, float* ws,
@@ -2759,8 +2743,7 @@ extern "C" int avc_backward_ragged(const avc_plan* p, const float* params, const
     if (p->compute != AVC_COMPUTE_F32)
         return fail(-8, "avc_backward_ragged: the plan computes with bf16 operand rounding, a forward-only model; gradients need the fp32 compute dtype "
                         "(avc_plan_set_compute_dtype(p, 0)) or a uniform plan");
-    if (seb < 0 || sec < 0 || (p->B - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
-        return fail(-1, "avc_backward_ragged: d_emb strides must be non-negative and span less than 2^31 elements");
+    if (int rc = check_row_strides("avc_backward_ragged", "d_emb", p->B, p->cfg.dec.c_cond, seb, sec)) return rc;
     return rag_backward_impl(p, d_emb, seb, sec, ws, (hipStream_t)stream);
 }
 
@@ -2772,71 +2755,30 @@ extern "C" int avc_backward_ragged(const avc_plan* p, const float* params, const
 static int rag_content_backward_impl(const avc_plan* p, const float* d_muls, float* ws, hipStream_t s) {
     const int B = p->B;
     const EncNet& e = p->enc;
-    const float SL = e.slope;
     const std::vector<avc_plan::RagLevel>& lv = p->rl_enc;
-    const int C = e.c.c_h, M = e.c.c_in;
-    const int* tab = (const int*)(ws + p->rag_tab);
-    float* gA = ws + p->gA2;
-    float* gC = ws + p->gC2;
-    float* dyA = ws + p->gA;
-    float* dyB = ws + p->gB;
-    // (every launch below asks for the 64 x 64 tile: a ragged tile is one sample's 64 frames, the mirrored instances exist on that tile only)
-    auto dgrad = [&](const LayerP& L, const float* dy, const avc_plan::RagLevel& sl, int cx, float* dx, const avc_plan::RagLevel& ol, int cout) {
-        ConvArgs a = mk_dgrad(SL, L, ws, dy, 0, -1, 1, 1, 1, 0, 64, dx, 0, 0, 1);
-        set_rag(a, tab, sl, cx, ol, ol, cout);
-        return a;
-    };
-    auto in_bwd_rows = [&](const float* g, long y, long st, const avc_plan::RagLevel& l, float* dy) {
-        RagINBwdArgs a;
-        memset(&a, 0, sizeof(a));
-        a.g = g; a.y = ws + y; a.mean = ws + st; a.rstd = ws + st + (long)B * C; a.dy = dy;
-        a.T = tab + l.dT; a.off = tab + l.doff;
-        a.B = B; a.C = C; a.slope = SL;
-        return avc_launch_rag_in_bwd(a, s);
-    };
+    const int C = e.c.c_h;
+    RagBwd c(p, ws, s, e.slope);
     {   // G_n = heads^T(d_muls): the caller's [2 c_out][Tz_s] blocks
-        ConvArgs a = dgrad(p->layers[e.heads], d_muls, lv[e.n], 2 * e.c.c_out, gA, lv[e.n], C);
-        RUN(avc_launch_conv(a, s, 11, p->tun));
+        ConvArgs a = rag_dgrad(c, p->layers[e.heads], d_muls, lv[e.n], 2 * e.c.c_out, c.gA, lv[e.n], C);
+        RUN(c.launch(a));
     }
     for (int l = e.n - 1; l >= 0; --l) {
         const int sub = e.c.subsample[l];
-        RUN(in_bwd_rows(gA, e.y2[l], e.st2[l], lv[l + 1], dyA));
+        RUN(rag_in_bwd(c, B, C, c.gA, e.y2[l], e.st2[l], lv[l + 1], c.dyA));
         {   // d(a1) = conv2^T(d(y2))
-            ConvArgs a = dgrad(p->layers[e.c2[l]], dyA, lv[l + 1], C, dyB, lv[l], C);
-            RUN(avc_launch_conv(a, s, 11, p->tun));
+            ConvArgs a = rag_dgrad(c, p->layers[e.c2[l]], c.dyA, lv[l + 1], C, c.dyB, lv[l], C);
+            RUN(c.launch(a));
         }
-        RUN(in_bwd_rows(dyB, e.y1[l], e.st1[l], lv[l], dyA));
+        RUN(rag_in_bwd(c, B, C, c.dyB, e.y1[l], e.st1[l], lv[l], c.dyA));
         {   // G_l = conv1^T(d(y1)) + pool^T(G_{l+1})
-            ConvArgs a = dgrad(p->layers[e.c1[l]], dyA, lv[l], C, gC, lv[l], C);
-            set_rag_res(a, tab, gA, sub > 1 ? AVC_RES_POOLT : AVC_RES_IDENTITY, lv[l + 1], C);
-            RUN(avc_launch_conv(a, s, 11, p->tun));
+            ConvArgs a = rag_dgrad(c, p->layers[e.c1[l]], c.dyA, lv[l], C, c.gC, lv[l], C);
+            set_rag_res(a, c.tab, c.gA, sub > 1 ? AVC_RES_POOLT : AVC_RES_IDENTITY, lv[l + 1], C);
+            RUN(c.launch(a));
         }
-        float* t = gA; gA = gC; gC = t;
+        std::swap(c.gA, c.gC);
     }
-    RUN(in_bwd_rows(gA, e.h0, e.st0, lv[0], dyA));
-    {   // d(cat) for the bank channels, masked by the bank's activations (cat > 0)
-        ConvArgs a = dgrad(p->layers[e.in_conv], dyA, lv[0], C, nullptr, lv[0], e.CC);
-        a.g[0].out2 = ws + e.dcat;
-        a.g[0].mask = ws + e.cat;
-        RUN(avc_launch_conv(a, s, 11, p->tun));
-    }
-    // d(x) = W_in[:, nb c_bank:]^T dy_in + sum_g pad_g^T(bank_g^T(dcat_g)): nb + 1 launches, each after the first adds the running sum through
-    // its residual join, in place -- a fixed order.  Stored as [T_b][M] rows: x's own layout.
-    float* dx = ws + e.dx;
-    {
-        ConvArgs a = dgrad(p->layers[e.in_pass], dyA, lv[0], C, dx, lv[0], M);
-        a.oc = 1; a.ot = M;
-        RUN(avc_launch_conv(a, s, 11, p->tun));
-    }
-    for (int g = 0; g < e.nb; ++g) {
-        ConvArgs a = dgrad(p->layers[e.bank[g]], ws + e.dcat, lv[0], e.CC, dx, lv[0], M);
-        a.rag.xc0 = g * e.c.c_bank;
-        a.oc = 1; a.ot = M;
-        set_rag_res(a, tab, dx, AVC_RES_IDENTITY, lv[0], M);
-        a.rc = 1; a.rt = M;
-        RUN(avc_launch_conv(a, s, 11, p->tun));
-    }
-    return 0;
+    RUN(rag_in_bwd(c, B, C, c.gA, e.h0, e.st0, lv[0], c.dyA));
+    return rag_enc_input_tail(c, e, lv[0], c.dyA);
 }
 
 extern "C" int avc_content_backward_ragged(const avc_plan* p, const float* params, const float* x, const float* d_muls, float* ws, void* stream) {
@@ -2860,59 +2802,37 @@ extern "C" int avc_content_backward_ragged(const avc_plan* p, const float* param
 static int rag_decoder_backward_impl(const avc_plan* p, const float* d_dec, float* ws, hipStream_t s) {
     const int N = p->Nd;
     const DecNet& d = p->dec;
-    const float SL = d.slope;
     const std::vector<avc_plan::RagLevel>& lv = p->rl_dec;
     const int C = d.c.c_h, Cz = d.c.c_in;
-    const long csb = (long)2 * d.n * 2 * C;
-    const int* tab = (const int*)(ws + p->rag_tab);
-    float* gA = ws + p->gA2;
-    float* gC = ws + p->gC2;
-    float* dyA = ws + p->gA;
-    float* dyB = ws + p->gB;
-    // (every ragged launch below asks for the 64 x 64 tile: a ragged tile is one sample's 64 frames, the mirrored instances exist on that tile only)
-    auto dgrad = [&](const LayerP& L, const float* dy, const avc_plan::RagLevel& sl, int cx, float* dx, const avc_plan::RagLevel& ol, int cout) {
-        ConvArgs a = mk_dgrad(SL, L, ws, dy, 0, -1, 1, 1, 1, 0, 64, dx, 0, 0, 1);
-        set_rag(a, tab, sl, cx, ol, ol, cout);
-        return a;
-    };
-    // coff < 0: plain InstanceNorm (the in_conv stage); up: planar store factor
-    auto in_bwd_rows = [&](const float* g, long y, long st, const avc_plan::RagLevel& l, int coff, int up, float* dy) {
-        RagINBwdArgs a;
-        memset(&a, 0, sizeof(a));
-        a.g = g; a.y = ws + y; a.mean = ws + st; a.rstd = ws + st + (long)N * C; a.dy = dy;
-        a.T = tab + l.dT; a.off = tab + l.doff;
-        a.B = N; a.C = C; a.slope = SL;
-        if (coff >= 0) { a.cond = ws + d.cond; a.dcond = ws + d.dcond; a.cond_sb = csb; a.cond_off = coff; a.up = up; }
-        return avc_launch_rag_in_bwd(a, s);
-    };
+    RagBwd c(p, ws, s, d.slope);
     {   // G_n = out_conv^T(d_dec): the caller's [M][T''_j] blocks
-        ConvArgs a = dgrad(p->layers[d.out_conv], d_dec, lv[d.n], p->M, gA, lv[d.n], C);
-        RUN(avc_launch_conv(a, s, 11, p->tun));
+        ConvArgs a = rag_dgrad(c, p->layers[d.out_conv], d_dec, lv[d.n], p->M, c.gA, lv[d.n], C);
+        RUN(c.launch(a));
     }
     for (int l = d.n - 1; l >= 0; --l) {
         const int up = d.c.upsample[l];
-        RUN(in_bwd_rows(gA, d.y2[l], d.st2[l], lv[l + 1], (2 * l + 1) * 2 * C, up, dyA));
+        RUN(rag_in_bwd(c, N, C, c.gA, d.y2[l], d.st2[l], lv[l + 1], c.dyA, (2 * l + 1) * 2 * C, up));
         {   // d(a1) = conv2^T(d(y2)): d(y2) lies as the conv's own output rows [C up][T_l] (C up off_l == C off_{l+1}: the same block starts)
-            ConvArgs a = dgrad(p->layers[d.c2[l]], dyA, lv[l], C * up, dyB, lv[l], C);
-            RUN(avc_launch_conv(a, s, 11, p->tun));
+            ConvArgs a = rag_dgrad(c, p->layers[d.c2[l]], c.dyA, lv[l], C * up, c.dyB, lv[l], C);
+            RUN(c.launch(a));
         }
-        RUN(in_bwd_rows(dyB, d.y1[l], d.st1[l], lv[l], (2 * l) * 2 * C, 1, dyA));
+        RUN(rag_in_bwd(c, N, C, c.dyB, d.y1[l], d.st1[l], lv[l], c.dyA, (2 * l) * 2 * C, 1));
         {   // G_l = conv1^T(d(y1)) + up^T(G_{l+1})
-            ConvArgs a = dgrad(p->layers[d.c1[l]], dyA, lv[l], C, gC, lv[l], C);
-            set_rag_res(a, tab, gA, up > 1 ? AVC_RES_UPT : AVC_RES_IDENTITY, lv[l + 1], C);
-            RUN(avc_launch_conv(a, s, 11, p->tun));
+            ConvArgs a = rag_dgrad(c, p->layers[d.c1[l]], c.dyA, lv[l], C, c.gC, lv[l], C);
+            set_rag_res(a, c.tab, c.gA, up > 1 ? AVC_RES_UPT : AVC_RES_IDENTITY, lv[l + 1], C);
+            RUN(c.launch(a));
         }
-        float* t = gA; gA = gC; gC = t;
+        std::swap(c.gA, c.gC);
     }
-    RUN(in_bwd_rows(gA, d.y0, d.st0, lv[0], -1, 1, dyA));
+    RUN(rag_in_bwd(c, N, C, c.gA, d.y0, d.st0, lv[0], c.dyA));
     {   // d(z): blocks [c_in][Tz_s] at c_in * offz[s]
-        ConvArgs a = dgrad(p->layers[d.in_conv], dyA, lv[0], C, ws + p->dz, lv[0], Cz);
-        RUN(avc_launch_conv(a, s, 11, p->tun));
+        ConvArgs a = rag_dgrad(c, p->layers[d.in_conv], c.dyA, lv[0], C, ws + p->dz, lv[0], Cz);
+        RUN(c.launch(a));
     }
     {   // d(emb)[b][i] = sum_o W[o][i] d(cond)[b][o]: the stacked affine layer's input gradient, "frames" = the N samples (d(cond) read with
         // channel stride 1, frame stride csb), stored row-major through the output strides -- the mirror image of the forward affine launch
-        const LayerP& La = p->layers[d.affine];
-        ConvArgs a = mk_dgrad(SL, La, ws, ws + d.dcond, 0, 1, (int)csb, 1, 1, N, N, ws + p->demb_rm, 0, 1, d.c.c_cond);
+        const long csb = (long)2 * d.n * 2 * C;
+        ConvArgs a = mk_dgrad(c.slope, p->layers[d.affine], ws, ws + d.dcond, 0, 1, (int)csb, 1, 1, N, N, ws + p->demb_rm, 0, 1, d.c.c_cond);
         RUN(avc_launch_conv(a, s, 0, p->tun));
     }
     return 0;
@@ -2939,7 +2859,6 @@ extern "C" int avc_decoder_backward_ragged(const avc_plan* p, const float* param
                         "gradients need fp32 (avc_plan_set_compute_dtype(p, 0)) or a uniform plan (avc_decoder_backward)");
     if (zc < p->cfg.dec.c_in)
         return fail(-1, "avc_decoder_backward_ragged: zc is too small: a latent block has at least c_in rows");
-    if (seb < 0 || sec < 0 || (p->Nd - 1) * seb + (p->cfg.dec.c_cond - 1) * sec >= (1L << 31))
-        return fail(-1, "avc_decoder_backward_ragged: emb strides must be non-negative and span less than 2^31 elements");
+    if (int rc = check_row_strides("avc_decoder_backward_ragged", "emb", p->Nd, p->cfg.dec.c_cond, seb, sec)) return rc;
     return rag_decoder_backward_impl(p, d_dec, ws, (hipStream_t)stream);
 }

@@ -95,6 +95,35 @@ def unpack_planar(p):
     return torch.stack((lo, hi), dim=3).reshape(p.shape[0], p.shape[1], 2 * p.shape[2])
 
 
+def _param_info(lib, h):
+    """(number of parameter tensors, [(offset, numel, shape)] of each in the flat parameter buffer) of a plan handle"""
+    info = []
+    for i in range(lib.avc_plan_num_params(h)):
+        off, n, dims = ctypes.c_long(), ctypes.c_long(), (ctypes.c_int * 3)()
+        lib.avc_plan_param_info(h, i, ctypes.byref(off), ctypes.byref(n), ctypes.byref(dims))
+        info.append((off.value, n.value, tuple(d for d in dims if d > 0)))
+    return len(info), info
+
+
+def _ints(v):
+    return (ctypes.c_int * len(v))(*v) if v else None
+
+
+def _packed(t, n, name, what, ws, at_least=False):
+    """t: a contiguous fp32 tensor of n (at_least: or more) elements on the workspace's device; what: its layout, for the message"""
+    if t.dtype != torch.float32 or t.device != ws.device or not t.is_contiguous() or (t.numel() < n if at_least else t.numel() != n):
+        raise ValueError(f"{name} must be a contiguous fp32 tensor of {'at least ' if at_least else ''}{n} elements on {ws.device}{what}")
+
+
+def _blocks(ws, off, c, lens):
+    """list of [c, len] views of the blocks that lie back to back in the workspace from float offset ``off``"""
+    out = []
+    for n in lens:
+        out.append(ws[off:off + c * n].view(c, n))
+        off += c * n
+    return out
+
+
 class Plan:
     """One (B, T, T_cond) launch plan.  ``lib`` defaults to the gfx950 library;
     tests may inject the CPU lane-level simulation build instead."""
@@ -164,16 +193,11 @@ class Plan:
         self.pair_storage = bh
         if not bh and self.lib.avc_plan_set_compute_dtype(h, 1 if operand_bf16 else 0) != 0:
             raise RuntimeError(self.lib.avc_last_error().decode())
-        self.num_params = self.lib.avc_plan_num_params(h)
+        self.num_params, self.param_info = _param_info(self.lib, h)
         self.param_floats = self.lib.avc_plan_param_floats(h)
         self.workspace_floats = self.lib.avc_plan_workspace_floats(h)
         self.out_len = self.lib.avc_plan_out_len(h)
         self.latent_len = self.lib.avc_plan_latent_len(h)
-        self.param_info = []
-        for i in range(self.num_params):
-            off, n, dims = ctypes.c_long(), ctypes.c_long(), (ctypes.c_int * 3)()
-            self.lib.avc_plan_param_info(h, i, ctypes.byref(off), ctypes.byref(n), ctypes.byref(dims))
-            self.param_info.append((off.value, n.value, tuple(d for d in dims if d > 0)))
 
     def close(self):
         """avc_plan_destroy: releases the plan's helper streams / events (the workspace is the caller's)."""
@@ -345,52 +369,50 @@ class RaggedPlan:
 
     MODES = {"pairs": 0, "speaker": _lib.PLAN_SPEAKER_ONLY, "emb": _lib.PLAN_EMB_INPUT}
     FAN_MODES = {"fanout": 0, "encode": _lib.PLAN_CONTENT_ONLY, "decode": _lib.PLAN_DECODER_ONLY}
+    # mode -> (which of T / T_cond are its lengths, whether src_of is allowed, (creator, flags) of the forward-only plan,
+    #          (creator, flags) with input_grads); None: there is no such plan
+    _EX, _FAN, _IG = "avc_plan_create_ragged_ex", "avc_plan_create_ragged_fanout", _lib.PLAN_INPUT_GRADS
+    KINDS = {"pairs": ("both", False, ("avc_plan_create_ragged", 0), (_EX, _IG)),
+             "speaker": ("T_cond", False, (_EX, MODES["speaker"]), (_EX, MODES["speaker"] | _IG)),
+             "emb": ("T", False, (_EX, MODES["emb"]), (_EX, MODES["emb"] | _IG)),
+             "fanout": ("T", True, (_FAN, FAN_MODES["fanout"]), None),
+             "encode": ("T", False, (_FAN, FAN_MODES["encode"]), ("avc_plan_create_ragged_content_grads", 0)),
+             "decode": ("T", True, (_FAN, FAN_MODES["decode"]), None),
+             "decode_ig": ("T", False, None, ("avc_plan_create_ragged_decoder_grads", 0))}
 
     def __init__(self, config, T, T_cond=None, lib=None, compute_dtype="fp32", device=None, tuning=None, mode="pairs", input_grads=False,
                  src_of=None):
         self.lib = lib if lib is not None else _lib.load()
         self.cfg = cfg_from_dict(config)
-        if mode not in self.MODES and mode not in self.FAN_MODES and mode != "decode_ig":
+        if mode not in self.KINDS:
             raise ValueError(f"mode must be one of {sorted(self.MODES) + sorted(self.FAN_MODES) + ['decode_ig']}, got {mode!r}")
+        lengths, takes_src_of, plain, with_grads = self.KINDS[mode]
         self.mode = mode
-        self.input_grads = bool(input_grads) or mode == "decode_ig"
+        self.input_grads = bool(input_grads) or plain is None
         self.src_of = None
-        if src_of is not None and mode not in ("fanout", "decode"):
+        if src_of is not None and not takes_src_of:
             raise ValueError(f"src_of belongs to plans of mode 'fanout' or 'decode' (this one is {mode!r})")
-        if mode == "decode_ig":
-            if not hasattr(self.lib, "avc_plan_create_ragged_decoder_grads"):
-                raise RuntimeError("the loaded library has no avc_plan_create_ragged_decoder_grads")
-            self.T = [int(t) for t in (T if T is not None else [])]
-            self.T_cond = []
-            self.B = len(self.T)
-        elif mode in self.FAN_MODES:
-            if self.input_grads and mode != "encode":
-                raise ValueError("fan-out plans are forward only (input_grads belongs to mode='speaker')")
-            if self.input_grads and not hasattr(self.lib, "avc_plan_create_ragged_content_grads"):
-                raise RuntimeError("the loaded library has no avc_plan_create_ragged_content_grads")
-            self.T = [int(t) for t in (T if T is not None else [])]
-            self.T_cond = []
-            self.B = len(self.T)
-            if mode != "encode":
-                self.src_of = [int(j) for j in (src_of if src_of is not None else range(self.B))]
-                if not self.src_of or any(not 0 <= j < self.B for j in self.src_of):
-                    raise ValueError(f"src_of must be a non-empty list of source indices in [0, {self.B}), got {self.src_of}")
-        elif mode == "speaker":
+        if self.input_grads and with_grads is None:
+            raise ValueError("fan-out plans are forward only (input_grads belongs to mode='speaker')")
+        creator, flags = with_grads if self.input_grads else plain
+        if not hasattr(self.lib, creator):   # (an older library)
+            raise RuntimeError(f"the loaded library has no {creator}")
+        if lengths == "T_cond":
             if T_cond is None:
                 raise ValueError("a 'speaker' plan takes the target lengths as T_cond (T is ignored)")
-            self.T_cond = [int(t) for t in T_cond]
-            self.T = []
-            self.B = len(self.T_cond)
-        elif mode == "emb":
-            self.T = [int(t) for t in T]
-            self.T_cond = []
-            self.B = len(self.T)
-        else:
+            self.T, self.T_cond = [], [int(t) for t in T_cond]
+        elif lengths == "both":
             self.T = [int(t) for t in T]
             self.T_cond = [int(t) for t in (T_cond if T_cond is not None else T)]
             if len(self.T) != len(self.T_cond):
                 raise ValueError("T and T_cond must be equally long, non-empty lists")
-            self.B = len(self.T)
+        else:
+            self.T, self.T_cond = [int(t) for t in (T if T is not None else [])], []
+        self.B = len(self.T) or len(self.T_cond)
+        if takes_src_of:
+            self.src_of = [int(j) for j in (src_of if src_of is not None else range(self.B))]
+            if not self.src_of or any(not 0 <= j < self.B for j in self.src_of):
+                raise ValueError(f"src_of must be a non-empty list of source indices in [0, {self.B}), got {self.src_of}")
         if not self.B:
             raise ValueError("T and T_cond must be equally long, non-empty lists")
         key = str(compute_dtype).lower()
@@ -398,24 +420,13 @@ class RaggedPlan:
             raise ValueError("ragged plans compute in fp32 or bf16 (operand rounding: the pair-storage engine takes uniform shapes)")
         h = ctypes.c_void_p()
         tun = _lib.make_tuning(self.lib, tuning)
-        arr = ctypes.c_int * self.B
         self.N = len(self.src_of) if self.src_of is not None else (0 if mode == "encode" else self.B)
+        lens = _ints(self.T)
+        args = {"avc_plan_create_ragged": (lens, _ints(self.T_cond)), self._EX: (lens, _ints(self.T_cond), flags),
+                self._FAN: (lens, self.N, _ints(self.src_of), flags)}.get(creator, (lens,))   # (the two *_grads creators take T alone)
         dev = torch.device(device) if device is not None else None
         with (torch.cuda.device(dev) if (dev is not None and dev.type == "cuda") else contextlib.nullcontext()):
-            if mode == "decode_ig":
-                rc = self.lib.avc_plan_create_ragged_decoder_grads(ctypes.byref(self.cfg), self.B, arr(*self.T), ctypes.byref(tun), ctypes.byref(h))
-            elif mode == "encode" and self.input_grads:
-                rc = self.lib.avc_plan_create_ragged_content_grads(ctypes.byref(self.cfg), self.B, arr(*self.T), ctypes.byref(tun), ctypes.byref(h))
-            elif mode in self.FAN_MODES:
-                rc = self.lib.avc_plan_create_ragged_fanout(ctypes.byref(self.cfg), self.B, arr(*self.T), self.N,
-                                                            (ctypes.c_int * self.N)(*self.src_of) if self.src_of is not None else None,
-                                                            self.FAN_MODES[mode], ctypes.byref(tun), ctypes.byref(h))
-            elif mode == "pairs" and not self.input_grads:
-                rc = self.lib.avc_plan_create_ragged(ctypes.byref(self.cfg), self.B, arr(*self.T), arr(*self.T_cond), ctypes.byref(tun), ctypes.byref(h))
-            else:
-                rc = self.lib.avc_plan_create_ragged_ex(ctypes.byref(self.cfg), self.B, arr(*self.T) if self.T else None,
-                                                        arr(*self.T_cond) if self.T_cond else None,
-                                                        self.MODES[mode] | (_lib.PLAN_INPUT_GRADS if self.input_grads else 0), ctypes.byref(tun), ctypes.byref(h))
+            rc = getattr(self.lib, creator)(ctypes.byref(self.cfg), self.B, *args, ctypes.byref(tun), ctypes.byref(h))
         if rc != 0:
             raise RuntimeError(self.lib.avc_last_error().decode())
         self.h = h
@@ -425,12 +436,7 @@ class RaggedPlan:
             raise RuntimeError(self.lib.avc_last_error().decode())
         self.param_floats = self.lib.avc_plan_param_floats(h)
         self.workspace_floats = self.lib.avc_plan_workspace_floats(h)
-        self.num_params = self.lib.avc_plan_num_params(h)
-        self.param_info = []
-        for i in range(self.num_params):
-            off, n, dims = ctypes.c_long(), ctypes.c_long(), (ctypes.c_int * 3)()
-            self.lib.avc_plan_param_info(h, i, ctypes.byref(off), ctypes.byref(n), ctypes.byref(dims))
-            self.param_info.append((off.value, n.value, tuple(d for d in dims if d > 0)))
+        self.num_params, self.param_info = _param_info(self.lib, h)
         self.out_len, self.out_off = [], []
         if mode not in ("speaker", "encode"):
             lens, offs = (ctypes.c_int * self.N)(), (ctypes.c_long * self.N)()
@@ -487,14 +493,15 @@ class RaggedPlan:
             raise RuntimeError(f"forward_emb needs a plan of mode 'emb' or 'fanout' (this one is {self.mode!r}: call "
                                f"{'forward_latents' if self.mode == 'decode' else 'forward'})")
         self._rows(x, self.T, "x")
-        emb = self._emb(emb, ws)
+        emb = self._strided_rows(emb, self.N, "emb", ws)
         with _on(ws):
             self._chk(self.lib.avc_forward_ragged_emb(self.h, _ptr(params), _ptr(x), _ptr(emb), emb.stride(0), emb.stride(1), _ptr(ws), _stream(ws)))
 
-    def _emb(self, emb, ws):
-        if emb.dim() != 2 or tuple(emb.shape) != (self.N, self.c_emb) or emb.dtype != torch.float32 or emb.device != ws.device:
-            raise ValueError(f"emb must be an fp32 [{self.N}, {self.c_emb}] tensor on {ws.device}")
-        return emb.contiguous() if (emb.stride(0) < 0 or emb.stride(1) < 0) else emb
+    def _strided_rows(self, t, rows, name, ws):
+        """t: fp32 [rows, c_cond] on the workspace's device, read in place through its strides (a copy where one is negative)"""
+        if t.dim() != 2 or tuple(t.shape) != (rows, self.c_emb) or t.dtype != torch.float32 or t.device != ws.device:
+            raise ValueError(f"{name} must be an fp32 [{rows}, {self.c_emb}] tensor on {ws.device}")
+        return t.contiguous() if (t.stride(0) < 0 or t.stride(1) < 0) else t
 
     def forward_latents(self, params, z, zc, emb, ws):
         """"decode" plans: z holds the S latent blocks back to back, block s = [zc][T[s]] fp32 (frames contiguous) at float offset
@@ -511,9 +518,8 @@ class RaggedPlan:
         zc = int(zc)
         if zc < self.c_lat:
             raise ValueError(f"zc must be at least {self.c_lat} ({self.c_lat}: mu-only blocks; {2 * self.c_lat}: mu | log_sigma blocks), got {zc}")
-        if z.dtype != torch.float32 or z.device != ws.device or not z.is_contiguous() or z.numel() < zc * sum(self.T):
-            raise ValueError(f"z must be a contiguous fp32 tensor of at least {zc * sum(self.T)} elements on {ws.device}")
-        return z, zc, self._emb(emb, ws)
+        _packed(z, zc * sum(self.T), "z", "", ws, at_least=True)
+        return z, zc, self._strided_rows(emb, self.N, "emb", ws)
 
     def backward_decoder(self, params, z, zc, emb, d_dec, ws):
         """``mode="decode_ig"`` plans, after ``forward_latents(params, z, zc, emb, ws)`` in the same workspace: d(loss)/d(z) and
@@ -524,20 +530,14 @@ class RaggedPlan:
             raise RuntimeError("backward_decoder needs RaggedPlan(mode='decode_ig') "
                                f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
         z, zc, emb = self._latents(z, zc, emb, ws)
-        n = self.n_mels * sum(self.out_len)
-        if d_dec.dtype != torch.float32 or d_dec.device != ws.device or not d_dec.is_contiguous() or d_dec.numel() != n:
-            raise ValueError(f"d_dec must be a contiguous fp32 tensor of {n} elements on {ws.device} (the layout of the plan's output blocks)")
+        _packed(d_dec, self.n_mels * sum(self.out_len), "d_dec", " (the layout of the plan's output blocks)", ws)
         with _on(ws):
             self._chk(self.lib.avc_decoder_backward_ragged(self.h, _ptr(params), _ptr(z), zc, _ptr(emb), emb.stride(0), emb.stride(1), _ptr(d_dec),
                                                            _ptr(ws), _stream(ws)))
 
     def d_z(self, ws):
         """list of [c_lat, T[s]] views of d(loss)/d(z_s) in the workspace (after ``backward_decoder``)"""
-        off, c, out = self.buffer("d_z"), self.c_lat, []
-        for n in self.T:
-            out.append(ws[off:off + c * n].view(c, n))
-            off += c * n
-        return out
+        return _blocks(ws, self.buffer("d_z"), self.c_lat, self.T)
 
     def d_emb(self, ws):
         """[N, c_cond] view of d(loss)/d(emb) in the workspace (after ``backward_decoder``): one row per output, always dense"""
@@ -549,10 +549,8 @@ class RaggedPlan:
         the content encoder; avc_plan_ragged_latents)"""
         if not self.lat_len:
             raise RuntimeError(f"a plan of mode {self.mode!r} has no content codes (or the loaded library has no avc_plan_ragged_latents)")
-        c = self.c_lat
-        mu = [ws[o:o + c * n].view(c, n) for o, n in zip(self.lat_off, self.lat_len)]
-        ls = [ws[o + c * n:o + 2 * c * n].view(c, n) for o, n in zip(self.lat_off, self.lat_len)]
-        return mu, ls
+        both = _blocks(ws, self.lat_off[0], 2 * self.c_lat, self.lat_len)   # (mu rows, then log_sigma rows)
+        return [b[:self.c_lat] for b in both], [b[self.c_lat:] for b in both]
 
     def backward(self, params, x_cond, d_emb, ws):
         """``mode="speaker", input_grads=True`` plans, after ``forward(params, None, x_cond, ws)`` in the same workspace: d(loss)/d(x_cond)
@@ -562,10 +560,7 @@ class RaggedPlan:
             raise RuntimeError("backward needs RaggedPlan(mode='speaker', input_grads=True): ragged plans are forward-only otherwise "
                                f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
         self._rows(x_cond, self.T_cond, "x_cond")
-        if d_emb.dim() != 2 or tuple(d_emb.shape) != (self.B, self.c_emb) or d_emb.dtype != torch.float32 or d_emb.device != ws.device:
-            raise ValueError(f"d_emb must be an fp32 [{self.B}, {self.c_emb}] tensor on {ws.device}")
-        if d_emb.stride(0) < 0 or d_emb.stride(1) < 0:
-            d_emb = d_emb.contiguous()
+        d_emb = self._strided_rows(d_emb, self.B, "d_emb", ws)
         with _on(ws):
             self._chk(self.lib.avc_backward_ragged(self.h, _ptr(params), _ptr(x_cond), _ptr(d_emb), d_emb.stride(0), d_emb.stride(1), _ptr(ws),
                                                    _stream(ws)))
@@ -579,9 +574,7 @@ class RaggedPlan:
             raise RuntimeError("backward_content needs RaggedPlan(mode='encode', input_grads=True) "
                                f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
         self._rows(x, self.T, "x")
-        n = 2 * self.c_lat * sum(self.lat_len)
-        if d_muls.dtype != torch.float32 or d_muls.device != ws.device or not d_muls.is_contiguous() or d_muls.numel() != n:
-            raise ValueError(f"d_muls must be a contiguous fp32 tensor of {n} elements on {ws.device} (the layout of the plan's latent blocks)")
+        _packed(d_muls, 2 * self.c_lat * sum(self.lat_len), "d_muls", " (the layout of the plan's latent blocks)", ws)
         with _on(ws):
             self._chk(self.lib.avc_content_backward_ragged(self.h, _ptr(params), _ptr(x), _ptr(d_muls), _ptr(ws), _stream(ws)))
 
@@ -604,4 +597,4 @@ class RaggedPlan:
 
     def outputs(self, ws):
         """list of [M, out_len[b]] views of the converted utterances in the workspace"""
-        return [ws[o:o + self.n_mels * n].view(self.n_mels, n) for o, n in zip(self.out_off, self.out_len)]
+        return _blocks(ws, self.out_off[0], self.n_mels, self.out_len) if self.out_len else []

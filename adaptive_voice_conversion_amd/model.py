@@ -270,7 +270,10 @@ class _PartFunction(torch.autograd.Function):
 
     @staticmethod
     def _begin(ctx, ae, mode, B, T, device):
-        entry = ae._entry(mode, B, T, T, device)
+        return _PartFunction._attach(ctx, ae, ae._entry(mode, B, T, T, device), device)
+
+    @staticmethod
+    def _attach(ctx, ae, entry, device):
         plan, ws = entry.plan, entry.ws
         if entry.busy():
             ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=device)   # private to this forward
@@ -316,23 +319,29 @@ class _SpeakerFunction(_PartFunction):
         return (None, dx) + _PartFunction._grads(ctx, g, "speaker")
 
 
-class _RaggedSpeakerFunction(torch.autograd.Function):
-    """``AE.get_speaker_embeddings_ragged`` with autograd with respect to its inputs (a "speaker" RaggedPlan with ``input_grads``): the
-    function's input is the packed [sum T, M] tensor ``_ragged_rows`` builds from the utterances -- torch's own autograd carries its
-    gradient back through the concatenation, device moves and views to every leaf that requires grad.  Parameters are frozen: they get
-    no gradient here (``speaker_encoder(x)`` on uniform shapes has them)."""
+class _RaggedFunction(_PartFunction):
+    """Shared steps of the ragged functions with autograd with respect to their inputs (RaggedPlans with ``input_grads``): the function's
+    inputs and outputs are PACKED tensors -- torch's own autograd carries their gradients through the concatenation, device moves and
+    views to every leaf that requires grad.  Parameters are frozen: they get no gradient here (the sub-modules on uniform shapes have
+    them)."""
+
+    @staticmethod
+    def _begin(ctx, ae, mode, T, Tc, device):
+        return _PartFunction._attach(ctx, ae, ae._ragged_plan(mode, T, Tc)[1], device)
+
+    @staticmethod
+    def _finish(ctx):
+        ctx.token.done = True
+
+
+class _RaggedSpeakerFunction(_RaggedFunction):
+    """``AE.get_speaker_embeddings_ragged`` (a "speaker" RaggedPlan with ``input_grads``): from the packed [sum T, M] tensor
+    ``_ragged_rows`` builds from the utterances to the [B, c_emb] embeddings."""
 
     @staticmethod
     def forward(ctx, ae, xc, Tc):
-        plan, entry = ae._ragged_plan("speaker_ig", (), Tc)
-        ws = entry.ws
-        if entry.busy():
-            ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=xc.device)   # private to this forward
-        token = _Token()
-        if ws is entry.ws:
-            entry.pending = weakref.ref(token)
+        plan, ws = _RaggedFunction._begin(ctx, ae, "speaker_ig", (), Tc, xc.device)
         plan.forward(ae._flat, None, xc, ws)
-        ctx.ae, ctx.plan, ctx.ws, ctx.token = ae, plan, ws, token
         ctx.save_for_backward(xc)
         return plan.emb(ws).clone()
 
@@ -343,27 +352,19 @@ class _RaggedSpeakerFunction(torch.autograd.Function):
         if d_emb.dtype != torch.float32:
             d_emb = d_emb.float()
         ctx.plan.backward(ctx.ae._flat, xc, d_emb, ctx.ws)
-        ctx.token.done = True
+        _RaggedFunction._finish(ctx)
         return None, ctx.plan.d_x_cond(ctx.ws).clone(), None
 
 
-class _RaggedContentFunction(torch.autograd.Function):
-    """``AE.content_encoder_ragged`` with autograd with respect to its inputs (an "encode" RaggedPlan with ``input_grads``), modelled on
-    ``_RaggedSpeakerFunction``: the function's input is the packed [sum T, M] tensor, its output the packed latents -- block s is
-    [2 c_lat][Tz_s], mu rows then log_sigma rows, the layout of ws["muls"].  The caller's per-utterance mu / log_sigma are views of that
-    output, so torch's own autograd gathers their gradients into the packed d_muls the plan reads.  Parameters are frozen."""
+class _RaggedContentFunction(_RaggedFunction):
+    """``AE.content_encoder_ragged`` (an "encode" RaggedPlan with ``input_grads``): from the packed [sum T, M] tensor to the packed
+    latents -- block s is [2 c_lat][Tz_s], mu rows then log_sigma rows, the layout of ws["muls"].  The caller's per-utterance mu /
+    log_sigma are views of that output, so torch's own autograd gathers their gradients into the packed d_muls the plan reads."""
 
     @staticmethod
     def forward(ctx, ae, x, T):
-        plan, entry = ae._ragged_plan("encode_ig", T, ())
-        ws = entry.ws
-        if entry.busy():
-            ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=x.device)   # private to this forward
-        token = _Token()
-        if ws is entry.ws:
-            entry.pending = weakref.ref(token)
+        plan, ws = _RaggedFunction._begin(ctx, ae, "encode_ig", T, (), x.device)
         plan.forward(ae._flat, x, None, ws)
-        ctx.ae, ctx.plan, ctx.ws, ctx.token = ae, plan, ws, token
         ctx.save_for_backward(x)
         o = plan.lat_off[0]
         return ws[o:o + 2 * plan.c_lat * sum(plan.lat_len)].clone()
@@ -373,27 +374,18 @@ class _RaggedContentFunction(torch.autograd.Function):
         _PartFunction._check(ctx)
         x, = ctx.saved_tensors
         ctx.plan.backward_content(ctx.ae._flat, x, d_muls.float().contiguous(), ctx.ws)
-        ctx.token.done = True
+        _RaggedFunction._finish(ctx)
         return None, ctx.plan.d_x(ctx.ws).clone(), None
 
 
-class _RaggedDecoderFunction(torch.autograd.Function):
-    """``AE.decoder_ragged`` with autograd with respect to its two inputs (a "decode_ig" RaggedPlan), modelled on
-    ``_RaggedContentFunction``: the function's inputs are the packed latents (block s = [c_lat][Tz_s]) and the [N, c_emb] embeddings (an
-    expanded single voice included), its output the packed [M][T''_j] blocks.  Torch's own autograd carries d_z back through the
-    concatenation to every latent leaf and sums the rows of an expanded voice.  Parameters are frozen."""
+class _RaggedDecoderFunction(_RaggedFunction):
+    """``AE.decoder_ragged`` (a "decode_ig" RaggedPlan): from the packed latents (block s = [c_lat][Tz_s]) and the [N, c_emb] embeddings
+    (an expanded single voice included, whose rows torch's own autograd sums) to the packed [M][T''_j] blocks."""
 
     @staticmethod
     def forward(ctx, ae, z, e, Tz):
-        plan, entry = ae._ragged_plan("decode_ig", Tz, ())
-        ws = entry.ws
-        if entry.busy():
-            ws = torch.zeros(plan.workspace_floats, dtype=torch.float32, device=z.device)   # private to this forward
-        token = _Token()
-        if ws is entry.ws:
-            entry.pending = weakref.ref(token)
+        plan, ws = _RaggedFunction._begin(ctx, ae, "decode_ig", Tz, (), z.device)
         plan.forward_latents(ae._flat, z, plan.c_lat, e, ws)
-        ctx.ae, ctx.plan, ctx.ws, ctx.token = ae, plan, ws, token
         ctx.save_for_backward(z, e)
         o = plan.out_off[0]
         return ws[o:o + plan.n_mels * sum(plan.out_len)].clone()
@@ -404,7 +396,7 @@ class _RaggedDecoderFunction(torch.autograd.Function):
         z, e = ctx.saved_tensors
         plan, ws = ctx.plan, ctx.ws
         plan.backward_decoder(ctx.ae._flat, z, plan.c_lat, e, d_dec.float().contiguous(), ws)
-        ctx.token.done = True
+        _RaggedFunction._finish(ctx)
         o = plan.buffer("d_z")
         return None, ws[o:o + plan.c_lat * sum(plan.T)].clone(), plan.d_emb(ws).clone(), None
 
