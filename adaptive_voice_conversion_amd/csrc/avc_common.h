@@ -264,6 +264,46 @@ struct RagINBwdArgs {
     int up;             // > 1: planar store, frame t of row c -> row c * up + t % up, frame t / up of the sample's [C * up][T_b / up] block
 };
 
+// ragged Conv1d weight gradient (conv_wgrad_ragged.hip): dW[co][ci][j] = sum_b sum_t dy_b[co][t] xpad_b[ci][t stride + j], db[co] = sum_b sum_t
+// dy_b[co][t] over packed rows of unequal length.  One JOB is one layer; a launch runs up to AVC_RWG_MAXJ jobs.  Both operands lie as
+// ConvRag lays them: sample b is a [channels][T_b] block at channels * off[b]; (xC, xc0) / (dyC, dyc0) = channels per block and first channel.
+// The K axis (b, t) is cut into chunks of 32 output frames of ONE sample -- chunk c = (chunk[2c], chunk[2c + 1]) = (sample, first frame), a
+// device table -- and workgroup (tile, z) walks chunks [z nchunks / nsplit, (z + 1) nchunks / nsplit) of its 64 co x 64 ci tile in table order.
+#define AVC_RWG_MAXJ 16
+struct RagWgJob {
+    const float* x;      // conv input rows (reflect padded on the fly at each sample's own edges)
+    const float* dy;     // output-gradient rows
+    const int* Tin;      // per sample: frames of x / first frame of its block (prefix sums)
+    const int* offin;
+    const int* Tout;     // ... of dy
+    const int* offout;
+    const int* chunk;
+    float* out;          // nsplit == 1: dW [Cout][Cin][KS], the parameter layout.  nsplit > 1: slot z at out + z slot_floats, weights in the
+    float* db;           // parameter layout followed by the Cout bias sums (avc_launch_rwg_reduce sums the slots in slot order).  db: nsplit == 1
+    long slot_floats;    // only, may be null
+    int xC, xc0, dyC, dyc0;
+    int Cin, Cout, KS, stride;
+    int nchunks, nsplit;
+    int ci_tiles, wg_begin;   // (launcher) 64-channel ci tiles; first workgroup of this job in its launch
+};
+struct RagWgArgs {
+    int njobs, pad_;
+    RagWgJob j[AVC_RWG_MAXJ];
+};
+// one layer's slots -> the flat gradient buffer: dw[i] = sum_z slab[z slot_floats + i] in ascending z, the bias sums behind the weights
+#define AVC_RWG_MAXR 32
+struct RagWgRed {
+    const float* slab;
+    float* dw;
+    float* db;           // may be null
+    long slot_floats, n_w;
+    int n_b, nsplit, blk_begin, pad_;
+};
+struct RagWgRedArgs {
+    int n, pad_;
+    RagWgRed it[AVC_RWG_MAXR];
+};
+
 struct INBwdArgs {
     const float* g;   // dL/d(out) rows [R][T]
     const float* y;   // conv output (pre-norm), as in forward

@@ -58,6 +58,13 @@ void avc_wgrad_geometry(WgradArgs& a);
 void avc_wgrad_plan_batch(WgradArgs* layers, int n, int target_wgs);
 int avc_launch_wgrad_batch(const WgradArgs* layers, int n, hipStream_t stream, int ablation = 0);   // the stream-K launches + the batch's reduce launch
 
+// ragged weight gradient (conv_wgrad_ragged.hip).  The split is a function of the layer and its chunk count alone, so a plan sizes the
+// slots at creation and every pass finds the same split.
+int avc_rwg_nsplit(int Cin, int Cout, int nchunks);
+long avc_rwg_slot_floats(int Cin, int Cout, int KS);
+int avc_launch_rwg(RagWgJob* jobs, int n, hipStream_t s);                 // any n: AVC_RWG_MAXJ jobs per launch
+int avc_launch_rwg_reduce(const RagWgRed* it, int n, hipStream_t s);      // any n: AVC_RWG_MAXR layers per launch
+
 int avc_launch_in_fwd(const INFwdArgs& a, hipStream_t s);
 int avc_launch_in_bwd(const INBwdArgs& a, hipStream_t s);
 // bf16 pair rows (rowops_pairs.hip): a.R = B * C / 2 dword rows

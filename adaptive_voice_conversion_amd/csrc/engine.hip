@@ -71,6 +71,8 @@ struct LayerP {
     long wplain = -1;                  // extra AVC_IMG_PLAIN forward image (the affine layer: its d_emb GEMM reads it as a [Kp][Mp] matrix)
     bool bh = false;                   // bf16 pair operands (AVC_PLAN_BF16S): AVC_IMG_K4H images over Cin / 2 (Cout / 2) dword channels
     long src_off = 0;                  // input-gradient image of input rows [src_off, src_off + dgM) of w[0] only (the in_conv's pass-through rows)
+    int rwg_nsplit = 1;                // avc_plan_create_ragged_speaker_grads: split-K ways of this layer's ragged weight gradient, and its slots
+    long rwg_slab = -1;
 };
 
 struct EncNet {
@@ -142,6 +144,8 @@ struct avc_plan {
         std::vector<int> T, off;   // per-sample frames, prefix sums (B + 1 entries)
         int ntiles = 0;
         long dT = -1, doff = -1, dtile = -1;   // workspace offsets (in floats == ints) of the device copies
+        long dchunk = -1;                      // avc_plan_create_ragged_speaker_grads: the weight gradient's K-chunks, (sample, first frame)
+        int nchunks = 0;                       // per 32 frames of one sample
     };
     std::vector<RagLevel> rl_spk, rl_enc, rl_dec;   // speaker / content encoder levels 0..n, decoder levels 0..n (rl_dec[0] == rl_enc[n])
     // fan-out plans (avc_plan_create_ragged_fanout): the decoder has a sample count of its own.  rl_z: the B SOURCES' latent level (the
@@ -149,6 +153,10 @@ struct avc_plan {
     // tiles: off is a gather, not a prefix sum); rl_dec: the Nd outputs.  Every other ragged plan: Nd == B, both are rl_dec[0].
     int Nd = 0;
     RagLevel rl_z, rl_map;
+    // avc_plan_create_ragged_speaker_grads: the dense stack's [C][B] rows as ONE sample of B frames (the Linears' weight gradients run on
+    // the ragged kernel too), and one d(pre-activation) row set per dense layer
+    RagLevel rl_dense;
+    std::vector<long> rag_dz;
     std::vector<int> rag_host;                      // host image of all tables (uploaded by avc_forward_ragged)
     long rag_tab = -1;
     avc_tuning tun;           // launch heuristics / diagnostic switches, captured at plan creation (the dry run sizes slabs and events with them)
@@ -2119,6 +2127,31 @@ extern "C" int avc_plan_create_ragged_decoder_grads(const avc_model_cfg* cfg, in
     return rag_plan_create(cfg, N, Tz, nullptr, AVC_PLAN_EMB_INPUT | AVC_PLAN_DECODER_ONLY | AVC_PLAN_INPUT_GRADS, 0, nullptr, tuning, out);
 }
 
+// The speaker encoder alone over B utterances WITH a backward pass that also computes its PARAMETER gradients (avc_backward_ragged_params):
+// the flagged speaker plan of avc_plan_create_ragged_ex plus the weight gradient's chunk tables and split-K slots and one d(pre-activation)
+// row set per dense layer.
+extern "C" int avc_plan_create_ragged_speaker_grads(const avc_model_cfg* cfg, int B, const int* T_cond, const avc_tuning* tuning, avc_plan** out) {
+    if (!cfg || !out || !T_cond || B < 1) return fail(-1, "avc_plan_create_ragged_speaker_grads: bad arguments (B >= 1 utterances of T_cond[b] frames)");
+    return rag_plan_create(cfg, B, nullptr, T_cond, AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_INPUT_GRADS | AVC_PLAN_PART_GRADS, 0, nullptr, tuning, out);
+}
+
+// the K-chunks of a level's weight gradient: 32 frames of one sample each, samples in order
+static void rag_chunks(avc_plan* p, avc_plan::RagLevel& L) {
+    std::vector<int> ch;
+    for (int b = 0; b < (int)L.T.size(); ++b)
+        for (int t0 = 0; t0 < L.T[b]; t0 += 32) {
+            ch.push_back(b);
+            ch.push_back(t0);
+        }
+    L.nchunks = (int)ch.size() / 2;
+    L.dchunk = rag_put(p, ch);
+}
+// split and slots of layer L's ragged weight gradient over the chunks of the level its output lives on
+static void rag_wgrad_slots(avc_plan* p, LayerP& L, const avc_plan::RagLevel& yl) {
+    L.rwg_nsplit = avc_rwg_nsplit(L.Cin, L.Cout, yl.nchunks);
+    if (L.rwg_nsplit > 1) L.rwg_slab = p->alloc((long)L.rwg_nsplit * avc_rwg_slot_floats(L.Cin, L.Cout, L.KS));
+}
+
 // flags: what avc_plan_flags reports, minus INFERENCE | RAGGED.  With AVC_PLAN_FANOUT the decoder runs over N samples mapped onto the B
 // sources by src_of; without it over the B sources themselves.
 static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const int* T_cond, int flags, int N, const int* src_of,
@@ -2300,6 +2333,23 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
         p->named["spk_h0"] = e.h0;
         rag_name_levels(p, "spk", e.n, {{"a1", e.a1}, {"a2", e.a2}});
         rag_name_levels(p, "spk", e.nd, {{"d1", e.d1}, {"d2", e.d2}});
+        if (flags & AVC_PLAN_PART_GRADS) {   // avc_backward_ragged_params: chunk tables, one dz row set per dense layer, the split-K slots
+            for (avc_plan::RagLevel& l : p->rl_spk) rag_chunks(p, l);
+            rag_level(p, p->rl_dense, std::vector<int>(1, B));
+            rag_chunks(p, p->rl_dense);
+            for (int l = 0; l < 2 * e.nd; ++l) p->rag_dz.push_back(p->alloc(C * Bl));
+            for (int id : e.bank) rag_wgrad_slots(p, p->layers[id], p->rl_spk[0]);
+            rag_wgrad_slots(p, p->layers[e.in_conv], p->rl_spk[0]);
+            for (int l = 0; l < e.n; ++l) {
+                rag_wgrad_slots(p, p->layers[e.c1[l]], p->rl_spk[l]);
+                rag_wgrad_slots(p, p->layers[e.c2[l]], p->rl_spk[l + 1]);
+            }
+            for (int l = 0; l < e.nd; ++l) {
+                rag_wgrad_slots(p, p->layers[e.dn1[l]], p->rl_dense);
+                rag_wgrad_slots(p, p->layers[e.dn2[l]], p->rl_dense);
+            }
+            rag_wgrad_slots(p, p->layers[e.outl], p->rl_dense);
+        }
     }
     if (do_enc) {
         alloc_enc(p->enc, p->rl_enc, false);
@@ -2697,21 +2747,77 @@ static int rag_enc_input_tail(const RagBwd& c, const EncNet& e, const avc_plan::
 //   input-gradient launches (ragged instances of conv_gemm_kernel; the pool adjoint of the residual path rides in the second one's
 //   epilogue) -> in_conv input gradient (d(cat), masked by the bank's activations) -> the nb + 1 terms of d(x_cond), summed through the
 //   residual join of consecutive launches into ws["d_x_cond"] in x_cond's own [sum T][M] layout.
-static int rag_backward_impl(const avc_plan* p, const float* d_emb, long seb, long sec, float* ws, hipStream_t s) {
+// avc_backward_ragged_params only (grads == NULL: the frozen pass records nothing): a layer's dy was just produced and its forward input is
+// saved -> one job of the next ragged weight-gradient launch (conv_wgrad_ragged.hip).  launch() goes out behind the phase that produced the
+// dy rows and before the ping-pong rows are overwritten; layers that were split leave partial slots, which ONE reduce launch at the end of
+// the pass sums in slot order into the flat gradient buffer.
+struct RagWg {
+    const avc_plan* p;
+    float* ws;
+    float* grads;
+    const int* tab;
+    hipStream_t s;
+    std::vector<RagWgJob> jobs;
+    std::vector<RagWgRed> reds;
+    // x: blocks of xC channels on level xl, the layer reads Cin of them from xc0; dy: blocks of dyC channels on level yl, Cout from dyc0
+    void add(const LayerP& L, const float* x, int xC, int xc0, const avc_plan::RagLevel& xl, const float* dy, int dyC, int dyc0,
+             const avc_plan::RagLevel& yl) {
+        if (!grads) return;
+        RagWgJob j;
+        memset(&j, 0, sizeof(j));
+        j.x = x; j.dy = dy;
+        j.Tin = tab + xl.dT; j.offin = tab + xl.doff; j.Tout = tab + yl.dT; j.offout = tab + yl.doff; j.chunk = tab + yl.dchunk;
+        j.xC = xC; j.xc0 = xc0; j.dyC = dyC; j.dyc0 = dyc0;
+        j.Cin = L.Cin; j.Cout = L.Cout; j.KS = L.KS; j.stride = L.stride;
+        j.nchunks = yl.nchunks; j.nsplit = L.rwg_nsplit;
+        j.slot_floats = avc_rwg_slot_floats(L.Cin, L.Cout, L.KS);
+        float* dw = grads + p->params[L.w[0]].off;
+        float* db = grads + p->params[L.b[0]].off;
+        j.out = j.nsplit > 1 ? ws + L.rwg_slab : dw;
+        j.db = db;
+        jobs.push_back(j);
+        if (j.nsplit > 1) {
+            RagWgRed r;
+            memset(&r, 0, sizeof(r));
+            r.slab = j.out; r.dw = dw; r.db = db;
+            r.slot_floats = j.slot_floats; r.n_w = (long)L.Cout * L.Cin * L.KS; r.n_b = L.Cout; r.nsplit = j.nsplit;
+            reds.push_back(r);
+        }
+    }
+    int launch() {
+        if (jobs.empty()) return 0;
+        const int rc = avc_launch_rwg(jobs.data(), (int)jobs.size(), s);
+        jobs.clear();
+        return rc;
+    }
+    int reduce() { return reds.empty() ? 0 : avc_launch_rwg_reduce(reds.data(), (int)reds.size(), s); }
+};
+
+static int rag_backward_impl(const avc_plan* p, const float* d_emb, long seb, long sec, float* ws, hipStream_t s, float* grads = nullptr) {
     const int B = p->B;
     const EncNet& e = p->spk;
     const std::vector<avc_plan::RagLevel>& lv = p->rl_spk;
     const int C = e.c.c_h;
     RagBwd c(p, ws, s, e.slope);
     const int* tab = c.tab;
+    RagWg w{p, ws, grads, tab, s, {}, {}};
     RUN(avc_launch_transpose_strided(ws + p->demb, d_emb, seb, sec, B, e.c.c_out, s));
     float* dhA = ws + p->dhA;
     {
         DenseArgs da = dense_stack_args(p, e, nullptr, ws, true);
         da.in = ws + p->demb;
         da.dpooled = dhA;
-        for (int l = 0; l < da.nlayers - 1; ++l) da.layer[l].dz = ws + p->dz;
+        for (int l = 0; l < da.nlayers - 1; ++l) da.layer[l].dz = ws + (grads ? p->rag_dz[l] : p->dz);
         RUN(avc_launch_dense(da, 1, s));
+        if (grads) {   // the 2 nd + 1 Linears: x and dz are [C][B] channel-major rows, ONE sample of B frames to the ragged kernel
+            const avc_plan::RagLevel& ld = p->rl_dense;
+            w.add(p->layers[e.outl], ws + e.hd[e.nd], C, 0, ld, ws + p->demb, e.c.c_out, 0, ld);
+            for (int l = e.nd - 1; l >= 0; --l) {
+                w.add(p->layers[e.dn2[l]], ws + e.d1[l], C, 0, ld, ws + p->rag_dz[2 * l + 1], C, 0, ld);
+                w.add(p->layers[e.dn1[l]], ws + e.hd[l], C, 0, ld, ws + p->rag_dz[2 * l], C, 0, ld);
+            }
+            RUN(w.launch());
+        }
     }
     RUN(avc_launch_rag_timepool_bwd(dhA, ws + e.a2[e.n - 1], tab + lv[e.n].dT, tab + lv[e.n].doff, B, C, lv[e.n].off[B], c.gA, c.dyA, c.slope, s));
     for (int l = e.n - 1; l >= 0; --l) {
@@ -2722,6 +2828,10 @@ static int rag_backward_impl(const avc_plan* p, const float* d_emb, long seb, lo
             a.g[0].mask = ws + e.a1[l];
             RUN(c.launch(a));
         }
+        // both dy rows of the block are live here and nowhere else: dW(conv2) = dyA x a1, dW(conv1) = dyB x out_l, one launch
+        w.add(p->layers[e.c2[l]], ws + e.a1[l], C, 0, lv[l], c.dyA, C, 0, lv[l + 1]);
+        w.add(p->layers[e.c1[l]], ws + e.out[l], C, 0, lv[l], c.dyB, C, 0, lv[l]);
+        RUN(w.launch());
         {   // G_l = conv1^T(dyB) + pool^T(G_{l+1}); dyA = G_l masked by the activation that produced out_l
             ConvArgs a = rag_dgrad(c, p->layers[e.c1[l]], c.dyB, lv[l], C, l > 0 ? c.gC : nullptr, lv[l], C);
             set_rag_res(a, tab, c.gA, sub > 1 ? AVC_RES_POOLT : AVC_RES_IDENTITY, lv[l + 1], C);
@@ -2731,7 +2841,31 @@ static int rag_backward_impl(const avc_plan* p, const float* d_emb, long seb, lo
         }
         std::swap(c.gA, c.gC);
     }
-    return rag_enc_input_tail(c, e, lv[0], c.dyA);
+    RUN(rag_enc_input_tail(c, e, lv[0], c.dyA));
+    if (!grads) return 0;
+    // d(cat) and cat hold the in_conv's and all bank members' operands at once: dW(in_conv) = dyA x cat, dW(bank g) = its slice of d(cat) x
+    // the M pass-through rows of cat (x itself) -- one launch; then every split layer's slots -> grads
+    w.add(p->layers[e.in_conv], ws + e.cat, e.CC, 0, lv[0], c.dyA, C, 0, lv[0]);
+    for (int g = 0; g < e.nb; ++g)
+        w.add(p->layers[e.bank[g]], ws + e.cat, e.CC, e.nb * e.c.c_bank, lv[0], ws + e.dcat, e.CC, g * e.c.c_bank, lv[0]);
+    RUN(w.launch());
+    return w.reduce();
+}
+
+// The ragged speaker backward WITH parameter gradients: rag_backward_impl plus one ragged weight-gradient launch behind each phase that
+// produces a layer's dy (the dense stack; each block; the in_conv and the bank together) and one reduce launch: 1 + n + 1 + 1 launches on
+// top of the frozen pass.  Overwrites exactly the speaker encoder's tensors of `grads`.
+extern "C" int avc_backward_ragged_params(const avc_plan* p, const float* params, const float* x_cond, const float* d_emb, long seb, long sec,
+                                          float* grads, float* ws, void* stream) {
+    if (!p || !params || !x_cond || !d_emb || !grads || !ws)
+        return fail(-1, "avc_backward_ragged_params: null argument (pass the plan, params, x_cond and workspace of the avc_forward_ragged this pass follows, d_emb [B, c_cond] and grads)");
+    if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_SPEAKER_ONLY) || !(p->flags & AVC_PLAN_INPUT_GRADS) || !(p->flags & AVC_PLAN_PART_GRADS))
+        return fail(-8, "avc_backward_ragged_params: the plan was not created by avc_plan_create_ragged_speaker_grads");
+    if (p->compute != AVC_COMPUTE_F32)
+        return fail(-8, "avc_backward_ragged_params: the avc_plan_create_ragged_speaker_grads plan computes with bf16 operand rounding, a forward-only model; "
+                        "gradients need fp32 (avc_plan_set_compute_dtype(p, 0)) or a uniform plan");
+    if (int rc = check_row_strides("avc_backward_ragged_params", "d_emb", p->B, p->cfg.dec.c_cond, seb, sec)) return rc;
+    return rag_backward_impl(p, d_emb, seb, sec, ws, (hipStream_t)stream, grads);
 }
 
 extern "C" int avc_backward_ragged(const avc_plan* p, const float* params, const float* x_cond, const float* d_emb, long seb, long sec, float* ws,

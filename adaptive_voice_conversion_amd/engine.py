@@ -330,7 +330,7 @@ class Plan:
 
 class RaggedPlan:
     """Launch plan of ONE pass over B utterances of DIFFERENT lengths (avc_plan_create_ragged_ex).  Nothing is padded.  Forward only,
-    except a "speaker" or an "encode" plan created with ``input_grads=True`` and a "decode_ig" plan (below).
+    except a "speaker" or an "encode" plan created with ``input_grads=True``, a "decode_ig" and a "speaker_pg" plan (below).
 
     mode "pairs" (default): B (source, target) pairs through all three networks, the batched form of
     ``Inferencer.inference_one_utterance`` (inference.py:54-70); result b equals ``AE.inference(x_b, x_cond_b)`` (model.py:387-391).
@@ -363,7 +363,12 @@ class RaggedPlan:
     (output j from latent j, no ``src_of``) and a backward pass with respect to its two inputs, parameters frozen, fp32 only: after
     ``forward_latents(params, z, zc, emb, ws)``, ``backward_decoder(params, z, zc, emb, d_dec, ws)`` leaves d(loss)/d(z) in ``d_z(ws)``
     and d(loss)/d(emb) in ``d_emb(ws)``.  Forward bit-identical to the "decode" plan; a larger workspace (weight images, row statistics,
-    d(cond), gradient rows).  ``buffer()`` names of the saved rows: "dec_y0", "dec_y1_<l>", "dec_a1_<l>", "dec_y2_<l>", their statistics
+    d(cond), gradient rows).
+
+    mode "speaker_pg" (avc_plan_create_ragged_speaker_grads; ``input_grads`` is implied): the "speaker" plan with input gradients whose
+    backward pass can also compute the speaker encoder's PARAMETER gradients: ``backward_params(params, x_cond, d_emb, grads, ws)`` writes
+    them into the flat buffer ``grads`` and leaves ``d_x_cond(ws)``; ``backward`` stays the frozen pass.  (A mode of its own, like
+    "decode_ig": ``mode="speaker", input_grads=True`` keeps its plan, workspace size and launches.)  ``buffer()`` names of the saved rows: "dec_y0", "dec_y1_<l>", "dec_a1_<l>", "dec_y2_<l>", their statistics
     "dec_st0", "dec_st1_<l>", "dec_st2_<l>", and "cond" / "d_cond".  (``mode="decode", input_grads=True`` keeps raising: fan-out plans,
     with their free ``src_of``, are forward only.)"""
 
@@ -378,14 +383,15 @@ class RaggedPlan:
              "fanout": ("T", True, (_FAN, FAN_MODES["fanout"]), None),
              "encode": ("T", False, (_FAN, FAN_MODES["encode"]), ("avc_plan_create_ragged_content_grads", 0)),
              "decode": ("T", True, (_FAN, FAN_MODES["decode"]), None),
-             "decode_ig": ("T", False, None, ("avc_plan_create_ragged_decoder_grads", 0))}
+             "decode_ig": ("T", False, None, ("avc_plan_create_ragged_decoder_grads", 0)),
+             "speaker_pg": ("T_cond", False, None, ("avc_plan_create_ragged_speaker_grads", 0))}
 
     def __init__(self, config, T, T_cond=None, lib=None, compute_dtype="fp32", device=None, tuning=None, mode="pairs", input_grads=False,
                  src_of=None):
         self.lib = lib if lib is not None else _lib.load()
         self.cfg = cfg_from_dict(config)
         if mode not in self.KINDS:
-            raise ValueError(f"mode must be one of {sorted(self.MODES) + sorted(self.FAN_MODES) + ['decode_ig']}, got {mode!r}")
+            raise ValueError(f"mode must be one of {sorted(self.MODES) + sorted(self.FAN_MODES) + ['decode_ig', 'speaker_pg']}, got {mode!r}")
         lengths, takes_src_of, plain, with_grads = self.KINDS[mode]
         self.mode = mode
         self.input_grads = bool(input_grads) or plain is None
@@ -399,7 +405,7 @@ class RaggedPlan:
             raise RuntimeError(f"the loaded library has no {creator}")
         if lengths == "T_cond":
             if T_cond is None:
-                raise ValueError("a 'speaker' plan takes the target lengths as T_cond (T is ignored)")
+                raise ValueError(f"a {mode!r} plan takes the target lengths as T_cond (T is ignored)")
             self.T, self.T_cond = [], [int(t) for t in T_cond]
         elif lengths == "both":
             self.T = [int(t) for t in T]
@@ -423,7 +429,8 @@ class RaggedPlan:
         self.N = len(self.src_of) if self.src_of is not None else (0 if mode == "encode" else self.B)
         lens = _ints(self.T)
         args = {"avc_plan_create_ragged": (lens, _ints(self.T_cond)), self._EX: (lens, _ints(self.T_cond), flags),
-                self._FAN: (lens, self.N, _ints(self.src_of), flags)}.get(creator, (lens,))   # (the two *_grads creators take T alone)
+                self._FAN: (lens, self.N, _ints(self.src_of), flags)}.get(creator, (_ints(self.T_cond) if lengths == "T_cond" else lens,))
+        # (the *_grads creators take their one list of lengths alone)
         dev = torch.device(device) if device is not None else None
         with (torch.cuda.device(dev) if (dev is not None and dev.type == "cuda") else contextlib.nullcontext()):
             rc = getattr(self.lib, creator)(ctypes.byref(self.cfg), self.B, *args, ctypes.byref(tun), ctypes.byref(h))
@@ -438,13 +445,13 @@ class RaggedPlan:
         self.workspace_floats = self.lib.avc_plan_workspace_floats(h)
         self.num_params, self.param_info = _param_info(self.lib, h)
         self.out_len, self.out_off = [], []
-        if mode not in ("speaker", "encode"):
+        if mode not in ("speaker", "speaker_pg", "encode"):
             lens, offs = (ctypes.c_int * self.N)(), (ctypes.c_long * self.N)()
             if self.lib.avc_plan_ragged_out(h, lens, offs) != 0:
                 raise RuntimeError(self.lib.avc_last_error().decode())
             self.out_len, self.out_off = list(lens), list(offs)
         self.lat_len, self.lat_off = [], []   # per SOURCE: latent frames and the float offset of its (mu | log_sigma) block in ws["muls"]
-        if mode not in ("speaker", "decode", "decode_ig") and hasattr(self.lib, "avc_plan_ragged_latents"):
+        if mode not in ("speaker", "speaker_pg", "decode", "decode_ig") and hasattr(self.lib, "avc_plan_ragged_latents"):
             lens, offs = (ctypes.c_int * self.B)(), (ctypes.c_long * self.B)()
             if self.lib.avc_plan_ragged_latents(h, lens, offs) != 0:
                 raise RuntimeError(self.lib.avc_last_error().decode())
@@ -473,7 +480,7 @@ class RaggedPlan:
             if x_cond is not None:
                 raise ValueError("an 'encode' plan runs the content encoder alone: forward(params, x, None, ws)")
             self._rows(x, self.T, "x")
-        elif self.mode == "speaker":
+        elif self.mode in ("speaker", "speaker_pg"):
             if x_cond is None:
                 raise ValueError("a 'speaker' plan reads x_cond: forward(params, None, x_cond, ws)")
             self._rows(x_cond, self.T_cond, "x_cond")
@@ -556,7 +563,7 @@ class RaggedPlan:
         """``mode="speaker", input_grads=True`` plans, after ``forward(params, None, x_cond, ws)`` in the same workspace: d(loss)/d(x_cond)
         from d_emb = d(loss)/d(emb), fp32 [B, c_cond] on the workspace's device, read in place whatever its (non-negative) strides (an
         expanded row included).  The result is ``d_x_cond(ws)``.  No parameter gradients; two calls give identical bits."""
-        if not (self.mode == "speaker" and self.input_grads):
+        if not (self.mode in ("speaker", "speaker_pg") and self.input_grads):
             raise RuntimeError("backward needs RaggedPlan(mode='speaker', input_grads=True): ragged plans are forward-only otherwise "
                                f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
         self._rows(x_cond, self.T_cond, "x_cond")
@@ -564,6 +571,21 @@ class RaggedPlan:
         with _on(ws):
             self._chk(self.lib.avc_backward_ragged(self.h, _ptr(params), _ptr(x_cond), _ptr(d_emb), d_emb.stride(0), d_emb.stride(1), _ptr(ws),
                                                    _stream(ws)))
+
+    def backward_params(self, params, x_cond, d_emb, grads, ws):
+        """``mode="speaker_pg"`` plans, after ``forward(params, None, x_cond, ws)`` in the same workspace: ``backward`` plus
+        d(loss)/d(parameters) of the speaker encoder, from the same pass.  ``grads``: a flat fp32 buffer of ``param_floats`` elements on the
+        workspace's device; the pass overwrites every speaker-encoder tensor in it (weights and biases) and nothing else.
+        ``d_x_cond(ws)`` is what ``backward`` leaves there, bit for bit.  fp32 only; two calls give identical bits."""
+        if self.mode != "speaker_pg":
+            raise RuntimeError("backward_params needs RaggedPlan(mode='speaker_pg') "
+                               f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
+        self._rows(x_cond, self.T_cond, "x_cond")
+        d_emb = self._strided_rows(d_emb, self.B, "d_emb", ws)
+        _packed(grads, self.param_floats, "grads", " (the flat parameter layout)", ws, at_least=True)
+        with _on(ws):
+            self._chk(self.lib.avc_backward_ragged_params(self.h, _ptr(params), _ptr(x_cond), _ptr(d_emb), d_emb.stride(0), d_emb.stride(1),
+                                                          _ptr(grads), _ptr(ws), _stream(ws)))
 
     def backward_content(self, params, x, d_muls, ws):
         """``mode="encode", input_grads=True`` plans, after ``forward(params, x, None, ws)`` in the same workspace: d(loss)/d(x) from

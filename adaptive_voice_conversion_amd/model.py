@@ -356,6 +356,30 @@ class _RaggedSpeakerFunction(_RaggedFunction):
         return None, ctx.plan.d_x_cond(ctx.ws).clone(), None
 
 
+class _RaggedSpeakerParamFunction(_RaggedFunction):
+    """``AE.speaker_encoder_ragged`` with live parameters (a "speaker_pg" RaggedPlan): the pattern of ``_SpeakerFunction`` on packed rows --
+    the speaker encoder's parameters are inputs of the function, their gradients and the packed input gradient come from ONE ragged
+    backward pass (``avc_backward_ragged_params``)."""
+
+    @staticmethod
+    def forward(ctx, ae, xc, Tc, *params):
+        plan, ws = _RaggedFunction._begin(ctx, ae, "speaker_pg", (), Tc, xc.device)
+        plan.forward(ae._flat, None, xc, ws)
+        ctx.save_for_backward(xc)
+        return plan.emb(ws).clone()
+
+    @staticmethod
+    def backward(ctx, d_emb):
+        _PartFunction._check(ctx)
+        xc, = ctx.saved_tensors
+        if d_emb.dtype != torch.float32:
+            d_emb = d_emb.float()
+        g = torch.empty_like(ctx.ae._flat)
+        ctx.plan.backward_params(ctx.ae._flat, xc, d_emb, g, ctx.ws)
+        dxc = ctx.plan.d_x_cond(ctx.ws).clone() if ctx.needs_input_grad[1] else None
+        return (None, dxc, None) + _PartFunction._grads(ctx, g, "speaker")
+
+
 class _RaggedContentFunction(_RaggedFunction):
     """``AE.content_encoder_ragged`` (an "encode" RaggedPlan with ``input_grads``): from the packed [sum T, M] tensor to the packed
     latents -- block s is [2 c_lat][Tz_s], mu rows then log_sigma rows, the layout of ws["muls"].  The caller's per-utterance mu /
@@ -635,7 +659,8 @@ class AE(nn.Module):
 
     def _ragged_plan(self, mode, T, Tc, src_of=None):
         """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all modes are kept.  modes "speaker_ig",
-        "encode_ig" and "decode_ig" (the speaker / content / decoder plan with input gradients) return (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
+        "encode_ig", "decode_ig" (the speaker / content / decoder plan with input gradients) and "speaker_pg" (the speaker plan whose
+        backward also computes its parameter gradients) return (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
         activations between a forward and its backward and is never the pooled one.  ``src_of`` (a tuple; "fanout" / "decode" plans):
         the source of every output, part of the key."""
         from .engine import RaggedPlan
@@ -645,9 +670,9 @@ class AE(nn.Module):
         if hit is None:
             # compute_dtype "bf16" -> "bf16r" here: the pair-STORAGE engine takes uniform shapes only; ragged plans round the operands of
             # the matrix products to bf16 on fp32 storage (engine.RaggedPlan).  The mode that ran is reported in `last_ragged_compute`.
-            ig = mode in ("speaker_ig", "encode_ig", "decode_ig")
+            ig = mode in ("speaker_ig", "encode_ig", "decode_ig", "speaker_pg")
             plan = RaggedPlan(self.config, T, Tc, lib=self._lib, compute_dtype="bf16r" if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")) else "fp32", device=dev,
-                              tuning=self._tuning, mode=mode[:-3] if (ig and mode != "decode_ig") else mode, input_grads=ig, src_of=src_of)
+                              tuning=self._tuning, mode=mode[:-3] if (ig and mode not in ("decode_ig", "speaker_pg")) else mode, input_grads=ig, src_of=src_of)
             if [(o, n) for o, n, _ in plan.param_info] != [(o, n) for o, n, _ in self._layout]:
                 raise RuntimeError("flat parameter layout of the C plan differs from the module's")
             hit = self._ragged[key] = (plan, _Entry(plan, torch.zeros(plan.workspace_floats, dtype=torch.float32, device=dev)) if ig else None)
@@ -883,6 +908,29 @@ class AE(nn.Module):
         plan, ws = self._ragged_plan("speaker", (), Tc)
         plan.forward(self._flat, None, xc, ws)
         return plan.emb(ws).clone()
+
+    def speaker_encoder_ragged(self, x_conds):
+        """``speaker_encoder(x)`` (the sub-module call) over utterances of DIFFERENT lengths in ONE launch set, the ragged counterpart beside
+        ``content_encoder_ragged`` and ``decoder_ragged``: x_conds is a list of [T'_b, M] tensors; returns [B, c_emb], bit-identical to
+        ``get_speaker_embeddings_ragged(x_conds)``.
+
+        Differentiable with respect to the speaker encoder's PARAMETERS and to its inputs: with grad enabled the result carries a
+        ``grad_fn`` when a speaker-encoder parameter or an utterance requires grad.  A backward then gives every speaker-encoder parameter
+        that requires grad its ``.grad`` (accumulated as torch accumulates; the other two networks' parameters get nothing) and every
+        utterance that requires grad its own -- all from ONE ragged backward pass in fp32 (``RaggedPlan(mode="speaker_pg")``,
+        avc_backward_ragged_params).  When no parameter requires grad the frozen pass of ``get_speaker_embeddings_ragged`` runs, with its
+        bits.  Workspace ownership, a second grad forward before a pending backward and the ``compute_dtype: bf16`` refusal are those of
+        ``get_speaker_embeddings_ragged``, which itself is unchanged: it stays forward-only while only parameters require grad."""
+        lo, hi = self._part_index["speaker"]
+        params = list(self.parameters())[lo:hi]
+        if not (torch.is_grad_enabled() and any(p.requires_grad for p in params)):
+            return self.get_speaker_embeddings_ragged(x_conds)
+        Tc, xc = self._ragged_rows(x_conds, "x_conds")
+        if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")):
+            raise RuntimeError("speaker_encoder_ragged: gradients through the ragged path are fp32 only, and compute_dtype is "
+                               f"{self.compute_dtype!r} (ragged plans then run 'bf16r', a forward-only rounding model).  Use the uniform path "
+                               "speaker_encoder(x_b) per utterance, or call under torch.no_grad()")
+        return _RaggedSpeakerParamFunction.apply(self, xc, Tc, *params)
 
     # ---- the three networks called on their own (SpeakerEncoder / ContentEncoder / Decoder.forward) --------
     def _part_grad(self, part, *inputs):

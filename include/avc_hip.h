@@ -343,7 +343,26 @@ int avc_decoder_forward_ragged(const avc_plan* p, const float* params, const flo
  * that was not created with both flags. */
 int avc_backward_ragged(const avc_plan* p, const float* params, const float* x_cond, const float* d_emb, long seb, long sec, float* ws,
                         void* stream);
-/* INPUT GRADIENTS THROUGH THE RAGGED CONTENT ENCODER: avc_plan_create_ragged_content_grads(cfg, S, T, tuning, out) creates the content
+/* PARAMETER GRADIENTS OF THE RAGGED SPEAKER ENCODER: avc_plan_create_ragged_speaker_grads(cfg, B, T_cond, tuning, out) creates the flagged
+ * speaker plan above (AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_INPUT_GRADS) with, on top of it, the weight gradient's K-chunk tables (32 frames of ONE
+ * utterance per chunk, next to the level tables), one d(pre-activation) row set per dense layer and the split-K slots of every layer that is
+ * split.  avc_plan_flags additionally reports AVC_PLAN_PART_GRADS.  Its forward (avc_forward_ragged) launches the same kernel instances on the
+ * same operands as the unflagged speaker plan: ws["emb"] is bit-identical.  avc_backward_ragged works on it as on the flagged plan (the frozen
+ * pass: no weight-gradient launch, ws["d_x_cond"] bit-identical to that plan's).  The existing creators keep refusing what they refused.
+ *   avc_backward_ragged_params follows an avc_forward_ragged on the SAME plan, params, x_cond and workspace; d_emb, seb, sec, params and x_cond
+ * as for avc_backward_ragged.  It is that pass plus d(loss)/d(parameters): behind each phase that produces a layer's output gradient, and
+ * before the ping-pong gradient rows are overwritten, one launch of the ragged weight-gradient kernel (csrc/conv_wgrad_ragged.hip; fp32 MFMA
+ * products): the 2 nd + 1 Linears of the dense stack together (their [c_h][B] rows are one sample of B frames), the two convs of every block
+ * together, the in_conv and all bank members together; then ONE reduce launch sums the split layers' slots in slot order: n + 3 launches on
+ * top of the frozen pass (9 for the stock 6 blocks).  `grads` is the full flat gradient buffer (the layout of params): the pass OVERWRITES
+ * every tensor of the speaker encoder's range (avc_plan_param_range(AVC_GRADS_SPEAKER); weights and biases) and touches nothing else.
+ * ws["d_x_cond"] is written as by avc_backward_ragged, bit for bit.  No atomics, a fixed summation order: two passes give identical bits.
+ * Every kernel goes to the caller's stream; the call only enqueues (no allocation, no copy from the host, no synchronisation).  fp32 only
+ * (-8 when the plan's compute dtype is bf16); -8 with a message naming the creator on any other plan; -1 on a null argument. */
+int avc_plan_create_ragged_speaker_grads(const avc_model_cfg* cfg, int B, const int* T_cond, const avc_tuning* tuning, avc_plan** out);
+int avc_backward_ragged_params(const avc_plan* p, const float* params, const float* x_cond, const float* d_emb, long seb, long sec,
+                               float* grads, float* ws, void* stream);
+/* INPUT GRADIENTS THROUGH THE RAGGED CONTENT ENCODER:avc_plan_create_ragged_content_grads(cfg, S, T, tuning, out) creates the content
  * encoder alone over S sources of T[s] frames -- the AVC_PLAN_CONTENT_ONLY plan of avc_plan_create_ragged_fanout -- with a backward pass
  * with respect to its input.  avc_plan_flags reports what that plan reports plus AVC_PLAN_INPUT_GRADS; avc_plan_ragged_latents works; the
  * reflect-pad rule is the forward plan's (-6).  Its forward runs through avc_forward_ragged(p, params, x, NULL, ws, stream) and launches
@@ -529,6 +548,17 @@ long avc_conv1d_wgrad_ws_floats(int B, int Cin, int Cout, int Tout, int KS);
 int avc_conv1d_wgrad(const float* x, long sxb, long sxc, int sxt, const float* dy, long syb, long syc, int syt, int yps,
                      int B, int Cin, int Cout, int Tin, int Tout, int KS, int stride, float* dW, float* db, float* ws,
                      void* stream);
+/* ... over B samples of DIFFERENT lengths T[b] (host array), each with its own reflect padding; Tout_b = ceil(T[b] / stride), stride 1 or 2,
+ * KS 1..8.  x and dy are packed as the ragged plans pack activations: sample b of x is a [xC][T[b]] block (frames contiguous) at float
+ * offset xC * sum(T[0..b)), of which the Cin channels from xc0 are read; dy likewise, [dyC][Tout_b] blocks, Cout channels from dyc0.  dW is
+ * [Cout][Cin][KS] (the parameter layout), db [Cout] or NULL; both are OVERWRITTEN.  ws: avc_conv1d_wgrad_ragged_ws_floats floats (-1 for bad
+ * arguments).  The call builds its length / offset / K-chunk tables itself and uploads them (a few KB) to the head of ws with ONE
+ * hipMemcpyAsync from pageable host memory on `stream`: it may block the host until the copy is staged and is NOT graph-capture safe; it
+ * allocates no device memory and does not synchronise the device.  fp32 MFMA products, no atomics, a fixed order: two calls give identical
+ * bits.  -6 when a sample is not longer than its left pad (KS / 2), -1 for any other bad argument. */
+long avc_conv1d_wgrad_ragged_ws_floats(int B, const int* T, int Cin, int Cout, int KS, int stride);
+int avc_conv1d_wgrad_ragged(const float* x, int xC, int xc0, const float* dy, int dyC, int dyc0, int B, const int* T, int Cin, int Cout,
+                            int KS, int stride, float* dW, float* db, float* ws, void* stream);
 /* nn.InstanceNorm1d(affine=False) (model.py:296,341) [+ append_cond model.py:77-83] [+ ReLU] [+ residual:
  * 1 identity, 2 avg-pool(ceil), 5 nearest x2]; cond row b: beta = cond[b*cond_sb + cond_off + c], gamma = [.. + C + c] */
 /* relu: 0 = no activation, 1 = ReLU, 2 = LeakyReLU(0.01) */
