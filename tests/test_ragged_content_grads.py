@@ -23,6 +23,7 @@ from adaptive_voice_conversion_amd import _lib as L
 from adaptive_voice_conversion_amd.engine import RaggedPlan, cfg_from_dict
 from oracle import avc_oracle as O
 from tests.emu_util import KINDS, backend
+from tests.ragged_oracle import content_levels as _levels, content_masks as _relu_masks
 from tests.redzone import GuardedOutput, guarded_input
 from tests.test_engine import flat_params
 from tests.test_input_grads import oracle_input_grads
@@ -37,14 +38,6 @@ def _leaves(xs, dev):
     return [x.to(dev, copy=True).requires_grad_(True) for x in xs]
 
 
-def _levels(cfg, T):
-    c = cfg["ContentEncoder"]
-    lv = [list(T)]
-    for s in c["subsample"][:c["n_conv_blocks"]]:
-        lv.append([-(-t // s) for t in lv[-1]])
-    return lv
-
-
 def _d_muls(plan, seed):
     """random upstream weights for mu and log_sigma in the layout of ws["muls"]: block s = [2 c_lat][Tz_s]"""
     return torch.randn(2 * plan.c_lat * sum(plan.lat_len), generator=torch.Generator().manual_seed(seed))
@@ -57,39 +50,6 @@ def _blocks(d, plan):
     for o, n in zip(plan.lat_off, plan.lat_len):
         blk = d[o - base:o - base + 2 * c * n].view(2 * c, n)
         out.append((blk[:c][None].clone(), blk[c:][None].clone()))
-    return out
-
-
-def _relu_masks(plan, ws, cfg):
-    """Per utterance the activation decisions (bool [1, C, T]) the engine took, in the oracle's forward call order (bank members,
-    in_conv-IN, per block IN1, IN2), read through ``plan.buffer()``: ``cat > 0`` for the bank, ``saved y > saved row mean`` for every
-    InstanceNorm stage.  Packed [channels][T_b] blocks per sample at channels * off[b]; statistics mean[B * C] | rstd[B * C], row b * C + c."""
-    c = plan.cfg.enc
-    nb, Cb, Ch = c.bank_size // c.bank_scale, c.c_bank, c.c_h
-    CC = nb * Cb + c.c_in
-    levels = _levels(cfg, plan.T)
-    offs = [[sum(lv[:b]) for b in range(plan.B)] for lv in levels]
-
-    def rows(name, level, b, ch, c0=0, nc=None):   # channels [c0, c0 + nc) of sample b's block
-        T = levels[level][b]
-        o = plan.buffer(name) + ch * offs[level][b] + c0 * T
-        return ws[o:o + (nc or ch) * T].view(1, nc or ch, T).cpu()
-
-    def stage(y, st, level, b):
-        o = plan.buffer(st) + b * Ch
-        mean = ws[o:o + Ch].cpu()
-        rstd = ws[o + plan.B * Ch:o + plan.B * Ch + Ch].cpu()
-        assert torch.isfinite(mean).all() and torch.isfinite(rstd).all() and (rstd > 0).all()
-        return rows(y, level, b, Ch) > mean[None, :, None]
-
-    out = []
-    for b in range(plan.B):
-        m = [rows("enc_cat", 0, b, CC, g * Cb, Cb) > 0 for g in range(nb)]
-        m.append(stage("enc_y0", "enc_st0", 0, b))
-        for l in range(c.n_conv_blocks):
-            m.append(stage(f"enc_y1_{l}", f"enc_st1_{l}", l, b))
-            m.append(stage(f"enc_y2_{l}", f"enc_st2_{l}", l + 1, b))
-        out.append(m)
     return out
 
 

@@ -27,11 +27,10 @@ from adaptive_voice_conversion_amd import _lib as L
 from adaptive_voice_conversion_amd.engine import RaggedPlan
 from oracle import avc_oracle as O
 from tests.emu_util import KINDS, backend
+from tests.ragged_oracle import content_masks, decoder_levels as _levels, decoder_masks as _dec_masks, decoder_oracle as _oracle, speaker_masks
 from tests.redzone import guarded_input
 from tests.test_engine import flat_params
-from tests.test_ragged_content_grads import _relu_masks as content_masks
 from tests.test_ragged_enroll import _model, _nan_ws, _setup, _utts
-from tests.test_ragged_input_grads import _relu_masks as speaker_masks
 from tests.test_submodules import rel
 
 BAR = 1e-4
@@ -65,75 +64,6 @@ def _d_dec(plan, seed):
 def _out_blocks(d, plan):
     M, base = plan.n_mels, plan.out_off[0]
     return [d[o - base:o - base + M * n].view(1, M, n) for o, n in zip(plan.out_off, plan.out_len)]
-
-
-def _levels(cfg, Tz):
-    d = cfg["Decoder"]
-    lv = [list(Tz)]
-    for u in d["upsample"][:d["n_conv_blocks"]]:
-        lv.append([t * u for t in lv[-1]])
-    return lv
-
-
-def _dec_masks(plan, ws, cfg):
-    """Per latent the activation decisions (bool [1, C, T]) the engine took, in the oracle's call order (in_conv-IN, per block AdaIN1,
-    AdaIN2), from the saved pre-norm rows, statistics and ws["cond"]; the first-stage masks are cross-checked against saved a1 > 0."""
-    d = cfg["Decoder"]
-    C, n, N = d["c_h"], d["n_conv_blocks"], plan.B
-    levels = _levels(cfg, plan.T)
-    offs = [[sum(lv[:b]) for b in range(N)] for lv in levels]
-    csb = 2 * n * 2 * C
-    o = plan.buffer("cond")
-    cond = ws[o:o + N * csb].view(N, csb).cpu()
-
-    def rows(name, level, b):
-        T = levels[level][b]
-        o = plan.buffer(name) + C * offs[level][b]
-        return ws[o:o + C * T].view(1, C, T).cpu()
-
-    def stats(name, b):
-        o = plan.buffer(name) + b * C
-        mean, rstd = ws[o:o + C].cpu(), ws[o + N * C:o + N * C + C].cpu()
-        assert torch.isfinite(mean).all() and torch.isfinite(rstd).all() and (rstd > 0).all()
-        return mean[None, :, None], rstd[None, :, None]
-
-    def ada(y, st, level, b, k):
-        mean, rstd = stats(st, b)
-        h = (rows(y, level, b) - mean) * rstd
-        beta, gamma = cond[b, 2 * k * C:(2 * k + 1) * C], cond[b, (2 * k + 1) * C:(2 * k + 2) * C]
-        return h.double() * gamma.double()[None, :, None] + beta.double()[None, :, None] > 0
-
-    out = []
-    for b in range(N):
-        m = [rows("dec_y0", 0, b) > stats("dec_st0", b)[0]]
-        for l in range(n):
-            m1 = ada(f"dec_y1_{l}", f"dec_st1_{l}", l, b, 2 * l)
-            assert torch.equal(m1, rows(f"dec_a1_{l}", l, b) > 0), (b, l)
-            m.append(m1)
-            m.append(ada(f"dec_y2_{l}", f"dec_st2_{l}", l + 1, b, 2 * l + 1))
-        out.append(m)
-    return out
-
-
-def _oracle(z, e, w, sd, cfg, masks, dtype):
-    """(d_z [c_lat, Tz], d_emb [c_emb], d_cond [2n, 2C]) of sum(w . decoder(z, e)) in ``dtype`` on the given branch.  The affine outputs
-    are made leaves by a zero weight and a bias that holds the affine output: the forward values are the same."""
-    n = cfg["Decoder"]["n_conv_blocks"]
-    sdd = {k: v.to(dtype) for k, v in sd.items()}
-    z = z.to(dtype)[None].clone().requires_grad_(True)
-    e = e.to(dtype)[None]
-    conds = []
-    for k in range(2 * n):
-        W, b = sdd[f"decoder.conv_affine_layers.{k}.weight"], sdd[f"decoder.conv_affine_layers.{k}.bias"]
-        c = (e @ W.t() + b)[0].clone().requires_grad_(True)
-        conds.append((c, W))
-        sdd[f"decoder.conv_affine_layers.{k}.weight"] = torch.zeros_like(W)
-        sdd[f"decoder.conv_affine_layers.{k}.bias"] = c
-    with O.relu_masks(masks):
-        (O.decoder(z, e, sdd, cfg) * w.to(dtype)).sum().backward()
-    d_cond = torch.stack([c.grad for c, _ in conds])
-    d_emb = sum(c.grad @ W for c, W in conds)
-    return z.grad[0].float(), d_emb.float(), d_cond.float()
 
 
 def _pass(kind, act="relu"):

@@ -16,6 +16,7 @@ from adaptive_voice_conversion_amd import _lib as L
 from adaptive_voice_conversion_amd.engine import RaggedPlan, cfg_from_dict
 from oracle import avc_oracle as O
 from tests.emu_util import KINDS, backend
+from tests.ragged_oracle import speaker_masks as _relu_masks
 from tests.test_engine import flat_params
 from tests.test_input_grads import oracle_input_grads
 from tests.test_ragged_enroll import _model, _nan_ws, _setup, _utts
@@ -45,38 +46,6 @@ def _plan_pass(kind, seed=9, d_seed=31):
     d = _d_emb(len(Tc), plan.c_emb, d_seed)
     plan.backward(params, xc, d.to(dev), ws)
     return plan, ws, params, cs, d, dev, cfg, sd
-
-
-def _relu_masks(plan, ws):
-    """Per utterance the list of activation decisions (bool [1, C, T] / [1, C]) the engine took, in the oracle's forward call order (bank
-    members, in_conv, per block conv1 / conv2, per dense block d1 / d2): read through ``plan.buffer()`` from the saved activations the
-    backward pass masks by -- packed [channels][T_b] blocks per sample at channels * off[b], dense rows channel-major [C][B]."""
-    c = plan.cfg.spk
-    nb, Cb, Ch = c.bank_size // c.bank_scale, c.c_bank, c.c_h
-    CC = nb * Cb + c.c_in
-    levels = [list(plan.T_cond)]
-    for l in range(c.n_conv_blocks):
-        levels.append([-(-t // c.subsample[l]) for t in levels[-1]])
-    offs = [[sum(lv[:b]) for b in range(plan.B)] for lv in levels]
-
-    def rows(name, level, b, ch, c0=0, nc=None):   # channels [c0, c0 + nc) of sample b's block
-        T = levels[level][b]
-        o = plan.buffer(name) + ch * offs[level][b] + c0 * T
-        return (ws[o:o + (nc or ch) * T].view(1, nc or ch, T) > 0).cpu()
-
-    out = []
-    for b in range(plan.B):
-        m = [rows("spk_cat", 0, b, CC, g * Cb, Cb) for g in range(nb)]
-        m.append(rows("spk_h0", 0, b, Ch))
-        for l in range(c.n_conv_blocks):
-            m.append(rows(f"spk_a1_{l}", l, b, Ch))
-            m.append(rows(f"spk_a2_{l}", l + 1, b, Ch))
-        for l in range(c.n_dense_blocks):
-            for k in ("d1", "d2"):
-                o = plan.buffer(f"spk_{k}_{l}")
-                m.append((ws[o:o + Ch * plan.B].view(Ch, plan.B)[:, b] > 0).cpu()[None])
-        out.append(m)
-    return out
 
 
 def _split(g, lens):

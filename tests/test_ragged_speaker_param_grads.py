@@ -18,26 +18,14 @@ from adaptive_voice_conversion_amd import _lib as L
 from adaptive_voice_conversion_amd.engine import Plan, RaggedPlan, cfg_from_dict
 from oracle import avc_oracle as O
 from tests.emu_util import KINDS, backend
+from tests.ragged_oracle import SPK, speaker_masks as _relu_masks, speaker_oracle as _oracle
 from tests.redzone import GuardedOutput, guarded_input, guarded_like
 from tests.test_engine import flat_params
 from tests.test_ragged_enroll import _model, _nan_ws, _setup, _utts
-from tests.test_ragged_input_grads import _d_emb, _leaves, _relu_masks
+from tests.test_ragged_input_grads import _d_emb, _leaves
 from tests.test_submodules import rel
 
-SPK = "speaker_encoder."
 _CACHE = {}
-
-
-def _oracle(cfg, sd, cs, masks, d, dtype):
-    """{name: d(sum_b <emb_b, d_b>)/d(parameter)} of O.speaker_encoder in `dtype`, utterance b on the branch masks[b]"""
-    leaves = {k: v.to(dtype).clone().requires_grad_(k.startswith(SPK)) for k, v in sd.items()}
-    total = 0
-    for b, c in enumerate(cs):
-        with O.relu_masks(masks[b]):
-            emb = O.speaker_encoder(c.t()[None].to(dtype), leaves, cfg)
-        total = total + (emb * d[b][None].to(dtype)).sum()
-    total.backward()
-    return {k: v.grad.double() for k, v in leaves.items() if k.startswith(SPK)}
 
 
 def _pass(kind, seed=9, d_seed=31):
