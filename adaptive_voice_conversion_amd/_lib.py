@@ -114,6 +114,16 @@ def declare(lib):
         lib.avc_conv1d_wgrad_ragged_ws_floats.restype = c_long
         lib.avc_conv1d_wgrad_ragged.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int,
                                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+    if hasattr(lib, "avc_plan_create_ragged_content_param_grads"):   # (likewise)
+        for name in ("avc_plan_create_ragged_content_param_grads", "avc_plan_create_ragged_decoder_param_grads"):
+            getattr(lib, name).argtypes = [ctypes.POINTER(ModelCfg), c_int, ctypes.POINTER(c_int), ctypes.POINTER(Tuning), ctypes.POINTER(c_void_p)]
+        lib.avc_content_backward_ragged_params.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.avc_decoder_backward_ragged_params.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p,
+                                                           c_void_p]
+        lib.avc_linear_wgrad_strided_ws_floats.argtypes = [c_int, c_int, c_int]
+        lib.avc_linear_wgrad_strided_ws_floats.restype = c_long
+        lib.avc_linear_wgrad_strided.argtypes = [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p]
     lib.avc_gather_segments.argtypes =[c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.avc_plan_destroy.argtypes = [c_void_p]
     lib.avc_plan_destroy.restype = None

@@ -285,6 +285,12 @@ struct RagWgJob {
     int Cin, Cout, KS, stride;
     int nchunks, nsplit;
     int ci_tiles, wg_begin;   // (launcher) 64-channel ci tiles; first workgroup of this job in its launch
+    // STRIDED one-sample jobs (KS = 1, stride = 1; strided = 0, the default: packed as above, nothing below is read).  The "frames" are the
+    // nframes rows of ONE matrix pair read through explicit element strides: x(ci, t) = x[ci sxc + t sxt], dy(co, t) = dy[co syc + t syt]
+    // (all >= 0; a frame stride of 0: every frame reads the same row).  No tables: chunk c = frames [32 c, 32 c + 32), nchunks =
+    // ceil(nframes / 32).  The decoder's AdaIN affine Linears: dy = a [N][2 C] slice of frame-major d(cond), x = the caller's emb.
+    int strided, nframes;
+    long sxc, sxt, syc, syt;
 };
 struct RagWgArgs {
     int njobs, pad_;

@@ -63,6 +63,8 @@ int avc_launch_wgrad_batch(const WgradArgs* layers, int n, hipStream_t stream, i
 int avc_rwg_nsplit(int Cin, int Cout, int nchunks);
 long avc_rwg_slot_floats(int Cin, int Cout, int KS);
 int avc_launch_rwg(RagWgJob* jobs, int n, hipStream_t s);                 // any n: AVC_RWG_MAXJ jobs per launch
+// a STRIDED one-sample job over N rows (x(n, ci) = x[n sxn + ci sxc], dy likewise); the caller sets out / db (and may lower nsplit to 1)
+void avc_rwg_strided_job(RagWgJob& j, const float* x, long sxn, long sxc, const float* dy, long syn, long syc, int N, int Cin, int Cout);
 int avc_launch_rwg_reduce(const RagWgRed* it, int n, hipStream_t s);      // any n: AVC_RWG_MAXR layers per launch
 
 int avc_launch_in_fwd(const INFwdArgs& a, hipStream_t s);

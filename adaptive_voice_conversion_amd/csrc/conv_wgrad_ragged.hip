@@ -32,7 +32,9 @@
 #define RWG_DYROW 33
 #define RWG_XROW 71   // >= 31 * 2 + 8, odd
 
-template <int KS>
+// SJ: a STRIDED one-sample job (RagWgJob::strided; KS = 1, stride = 1): only the staging differs -- the chunks, the MFMA chain, the slots and
+// the stores are the packed job's, so at packed strides the two give the same bits.
+template <int KS, bool SJ = false>
 static __device__ __forceinline__ void rwg_body(const RagWgJob& J, int local, float* sdy, float* sx) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, h = lane >> 5;
@@ -55,23 +57,42 @@ static __device__ __forceinline__ void rwg_body(const RagWgJob& J, int local, fl
     float bsum = 0.f;
 
     for (int c = c_lo; c < c_hi; ++c) {
-        const int b = J.chunk[2 * c], t0 = J.chunk[2 * c + 1];
-        const int Tin = J.Tin[b], Tout = J.Tout[b];
-        const float* xb = J.x + (long)J.xC * J.offin[b] + (long)J.xc0 * Tin;
-        const float* yb = J.dy + (long)J.dyC * J.offout[b] + (long)J.dyc0 * Tout;
-        for (int i = tid; i < 64 * 32; i += RWG_THREADS) {
-            const int r = i >> 5, t = i & 31;
-            const int co = co0 + r, tt = t0 + t;
-            sdy[r * RWG_DYROW + t] = (co < J.Cout && tt < Tout) ? yb[(long)co * Tout + tt] : 0.f;
-        }
-        for (int i = tid; i < 64 * XSEG; i += RWG_THREADS) {
-            const int r = i / XSEG, q = i - r * XSEG;
-            const int ci = ci0 + r;
-            int f = t0 * stride + q - padL;
-            f = f < 0 ? -f : f;
-            f = f >= Tin ? 2 * (Tin - 1) - f : f;
-            // (a frame still outside after one reflection belongs to output frames past the sample's end: dy is zero there)
-            sx[r * RWG_XROW + q] = (ci < J.Cin && f >= 0 && f < Tin) ? xb[(long)ci * Tin + f] : 0.f;
+        if constexpr (SJ) {
+            // No tables, no reflection (KS = 1): chunk c = frames [32 c, 32 c + 32) of the one sample.  The lane order of each staging loop
+            // follows the operand's unit-stride axis, so a wave's loads stay coalesced: channels fastest where the channel stride is 1
+            // (frame-major d(cond), a row-major emb, an expanded single voice), frames fastest otherwise.  The LDS rows keep their odd strides:
+            // 32 consecutive channels at one frame fall into 32 different banks (33 = 1, 71 = 7 mod 32), as 32 consecutive frames of a row do.
+            const int t0 = 32 * c, N = J.nframes;
+            const bool ych = (J.syc == 1 && J.syt != 1), xch = (J.sxc == 1 && J.sxt != 1);   // block-uniform
+            for (int i = tid; i < 64 * 32; i += RWG_THREADS) {
+                const int r = ych ? (i & 63) : (i >> 5), t = ych ? (i >> 6) : (i & 31);
+                const int co = co0 + r, tt = t0 + t;
+                sdy[r * RWG_DYROW + t] = (co < J.Cout && tt < N) ? J.dy[(long)co * J.syc + (long)tt * J.syt] : 0.f;
+            }
+            for (int i = tid; i < 64 * 32; i += RWG_THREADS) {
+                const int r = xch ? (i & 63) : (i >> 5), q = xch ? (i >> 6) : (i & 31);
+                const int ci = ci0 + r, f = t0 + q;
+                sx[r * RWG_XROW + q] = (ci < J.Cin && f < N) ? J.x[(long)ci * J.sxc + (long)f * J.sxt] : 0.f;
+            }
+        } else {
+            const int b = J.chunk[2 * c], t0 = J.chunk[2 * c + 1];
+            const int Tin = J.Tin[b], Tout = J.Tout[b];
+            const float* xb = J.x + (long)J.xC * J.offin[b] + (long)J.xc0 * Tin;
+            const float* yb = J.dy + (long)J.dyC * J.offout[b] + (long)J.dyc0 * Tout;
+            for (int i = tid; i < 64 * 32; i += RWG_THREADS) {
+                const int r = i >> 5, t = i & 31;
+                const int co = co0 + r, tt = t0 + t;
+                sdy[r * RWG_DYROW + t] = (co < J.Cout && tt < Tout) ? yb[(long)co * Tout + tt] : 0.f;
+            }
+            for (int i = tid; i < 64 * XSEG; i += RWG_THREADS) {
+                const int r = i / XSEG, q = i - r * XSEG;
+                const int ci = ci0 + r;
+                int f = t0 * stride + q - padL;
+                f = f < 0 ? -f : f;
+                f = f >= Tin ? 2 * (Tin - 1) - f : f;
+                // (a frame still outside after one reflection belongs to output frames past the sample's end: dy is zero there)
+                sx[r * RWG_XROW + q] = (ci < J.Cin && f >= 0 && f < Tin) ? xb[(long)ci * Tin + f] : 0.f;
+            }
         }
         __syncthreads();
         if (active) {
@@ -120,6 +141,10 @@ __global__ void __launch_bounds__(RWG_THREADS) conv_wgrad_ragged_kernel(const Ra
     for (int i = 1; i < A.njobs; ++i) ji = ((int)blockIdx.x >= A.j[i].wg_begin) ? i : ji;
     const RagWgJob& J = A.j[ji];
     const int local = (int)blockIdx.x - J.wg_begin;
+    if (J.strided) {   // (block-uniform, like the tap count below)
+        rwg_body<1, true>(J, local, sdy, sx);
+        return;
+    }
     switch (J.KS) {   // (block-uniform: the taps are a compile-time count inside, the accumulators stay in registers)
         case 1: rwg_body<1>(J, local, sdy, sx); break;
         case 2: rwg_body<2>(J, local, sdy, sx); break;
@@ -167,6 +192,9 @@ int avc_launch_rwg(RagWgJob* jobs, int n, hipStream_t s) {
             RagWgJob& j = jobs[i];
             if (j.KS < 1 || j.KS > 8 || j.stride < 1 || j.stride > 2 || j.nsplit < 1 || j.nchunks < 1 || j.Cin < 1 || j.Cout < 1) return -1;
             if (j.nsplit > j.nchunks || (j.nsplit > 1 && j.slot_floats < (long)j.Cout * j.Cin * j.KS + j.Cout)) return -1;
+            if (j.strided && (j.KS != 1 || j.stride != 1 || j.nframes < 1 || j.nchunks != avc_cdiv(j.nframes, 32) || j.sxc < 0 || j.sxt < 0 ||
+                              j.syc < 0 || j.syt < 0))
+                return -1;
             j.ci_tiles = avc_cdiv(j.Cin, 64);
             j.wg_begin = wgs;
             wgs += avc_cdiv(j.Cout, 64) * j.ci_tiles * j.nsplit;
@@ -277,5 +305,50 @@ extern "C" int avc_conv1d_wgrad_ragged(const float* x, int xC, int xc0, const fl
     memset(&r, 0, sizeof(r));
     r.slab = j.out; r.dw = dW; r.db = db;
     r.slot_floats = j.slot_floats; r.n_w = (long)Cout * Cin * KS; r.n_b = Cout; r.nsplit = j.nsplit;
+    return avc_launch_rwg_reduce(&r, 1, s);
+}
+
+// ---- op level: a Linear's weight gradient over N rows read through strides -------------------------------------------------------------
+//     dW[co][ci] = sum_n dy(n, co) x(n, ci),   db[co] = sum_n dy(n, co),     x(n, ci) = x[n sxn + ci sxc],   dy(n, co) = dy[n syn + co syc]
+// ONE strided job of the kernel above (the N rows are its frames).  The walk is avc_conv1d_wgrad_ragged's at B = 1, T = N, KS = 1: with
+// sxn = syn = 1, sxc = syc = N the two give the same bits.
+static int rwg_strided_check(long sxn, long sxc, long syn, long syc, int N, int Cin, int Cout) {
+    if (N < 1 || Cin < 1 || Cout < 1 || sxn < 0 || sxc < 0 || syn < 0 || syc < 0) return -1;
+    if ((N - 1) * sxn + (Cin - 1) * sxc >= (1L << 31) || (N - 1) * syn + (Cout - 1) * syc >= (1L << 31)) return -1;
+    return 0;
+}
+
+void avc_rwg_strided_job(RagWgJob& j, const float* x, long sxn, long sxc, const float* dy, long syn, long syc, int N, int Cin, int Cout) {
+    memset(&j, 0, sizeof(j));
+    j.x = x; j.dy = dy;
+    j.strided = 1; j.nframes = N;
+    j.sxc = sxc; j.sxt = sxn; j.syc = syc; j.syt = syn;
+    j.Cin = Cin; j.Cout = Cout; j.KS = 1; j.stride = 1;
+    j.nchunks = avc_cdiv(N, 32);
+    j.nsplit = avc_rwg_nsplit(Cin, Cout, j.nchunks);
+    j.slot_floats = avc_rwg_slot_floats(Cin, Cout, 1);
+}
+
+extern "C" long avc_linear_wgrad_strided_ws_floats(int N, int Cin, int Cout) {
+    if (N < 1 || Cin < 1 || Cout < 1) return -1;
+    const int ns = avc_rwg_nsplit(Cin, Cout, avc_cdiv(N, 32));
+    return 64 + (ns > 1 ? (long)ns * avc_rwg_slot_floats(Cin, Cout, 1) : 0);
+}
+
+extern "C" int avc_linear_wgrad_strided(const float* x, long sxn, long sxc, const float* dy, long syn, long syc, int N, int Cin, int Cout, float* dW,
+                                        float* db, float* ws, void* stream) {
+    if (!x || !dy || !dW || !ws) return -1;
+    if (int rc = rwg_strided_check(sxn, sxc, syn, syc, N, Cin, Cout)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    RagWgJob j;
+    avc_rwg_strided_job(j, x, sxn, sxc, dy, syn, syc, N, Cin, Cout);
+    j.out = j.nsplit > 1 ? ws + 64 : dW;
+    j.db = db;
+    if (int rc = avc_launch_rwg(&j, 1, s)) return rc;
+    if (j.nsplit == 1) return 0;
+    RagWgRed r;
+    memset(&r, 0, sizeof(r));
+    r.slab = j.out; r.dw = dW; r.db = db;
+    r.slot_floats = j.slot_floats; r.n_w = (long)Cout * Cin; r.n_b = Cout; r.nsplit = j.nsplit;
     return avc_launch_rwg_reduce(&r, 1, s);
 }

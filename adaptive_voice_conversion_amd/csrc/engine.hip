@@ -71,8 +71,8 @@ struct LayerP {
     long wplain = -1;                  // extra AVC_IMG_PLAIN forward image (the affine layer: its d_emb GEMM reads it as a [Kp][Mp] matrix)
     bool bh = false;                   // bf16 pair operands (AVC_PLAN_BF16S): AVC_IMG_K4H images over Cin / 2 (Cout / 2) dword channels
     long src_off = 0;                  // input-gradient image of input rows [src_off, src_off + dgM) of w[0] only (the in_conv's pass-through rows)
-    int rwg_nsplit = 1;                // avc_plan_create_ragged_speaker_grads: split-K ways of this layer's ragged weight gradient, and its slots
-    long rwg_slab = -1;
+    int rwg_nsplit = 1;                // ragged plans with AVC_PLAN_PART_GRADS: split-K ways of this layer's ragged weight gradient, and its
+    long rwg_slab = -1;                // slots (a stacked layer: one set of slots per source tensor, back to back)
 };
 
 struct EncNet {
@@ -157,7 +157,10 @@ struct avc_plan {
     // the ragged kernel too), and one d(pre-activation) row set per dense layer
     RagLevel rl_dense;
     std::vector<long> rag_dz;
-    std::vector<int> rag_host;                      // host image of all tables (uploaded by avc_forward_ragged)
+    // avc_plan_create_ragged_content_param_grads / _decoder_param_grads: one more set of gradient rows -- conv1's dy of a block, so that it
+    // does not overwrite conv2's (gA) before the block's one weight-gradient launch has read both
+    long rag_dy1 = -1;
+    std::vector<int> rag_host;                     // host image of all tables (uploaded by avc_forward_ragged)
     long rag_tab = -1;
     avc_tuning tun;           // launch heuristics / diagnostic switches, captured at plan creation (the dry run sizes slabs and events with them)
     int nev_need = 0;         // events one backward pass records on the wgrad streams
@@ -2135,6 +2138,20 @@ extern "C" int avc_plan_create_ragged_speaker_grads(const avc_model_cfg* cfg, in
     return rag_plan_create(cfg, B, nullptr, T_cond, AVC_PLAN_SPEAKER_ONLY | AVC_PLAN_INPUT_GRADS | AVC_PLAN_PART_GRADS, 0, nullptr, tuning, out);
 }
 
+// The content encoder alone over S sources WITH a backward pass that also computes its PARAMETER gradients
+// (avc_content_backward_ragged_params): the plan of avc_plan_create_ragged_content_grads plus the weight gradient's chunk tables on every
+// level, one more set of gradient rows and the split-K slots.
+extern "C" int avc_plan_create_ragged_content_param_grads(const avc_model_cfg* cfg, int S, const int* T, const avc_tuning* tuning, avc_plan** out) {
+    if (!cfg || !out || !T || S < 1) return fail(-1, "avc_plan_create_ragged_content_param_grads: bad arguments (S >= 1 sources of T[s] frames)");
+    return rag_plan_create(cfg, S, T, nullptr, AVC_PLAN_FANOUT | AVC_PLAN_CONTENT_ONLY | AVC_PLAN_INPUT_GRADS | AVC_PLAN_PART_GRADS, 0, nullptr, tuning, out);
+}
+
+// ... and the decoder alone over N latents (avc_decoder_backward_ragged_params): the plan of avc_plan_create_ragged_decoder_grads plus the same.
+extern "C" int avc_plan_create_ragged_decoder_param_grads(const avc_model_cfg* cfg, int N, const int* Tz, const avc_tuning* tuning, avc_plan** out) {
+    if (!cfg || !out || !Tz || N < 1) return fail(-1, "avc_plan_create_ragged_decoder_param_grads: bad arguments (N >= 1 latents of Tz[j] frames)");
+    return rag_plan_create(cfg, N, Tz, nullptr, AVC_PLAN_EMB_INPUT | AVC_PLAN_DECODER_ONLY | AVC_PLAN_INPUT_GRADS | AVC_PLAN_PART_GRADS, 0, nullptr, tuning, out);
+}
+
 // the K-chunks of a level's weight gradient: 32 frames of one sample each, samples in order
 static void rag_chunks(avc_plan* p, avc_plan::RagLevel& L) {
     std::vector<int> ch;
@@ -2147,10 +2164,13 @@ static void rag_chunks(avc_plan* p, avc_plan::RagLevel& L) {
     L.dchunk = rag_put(p, ch);
 }
 // split and slots of layer L's ragged weight gradient over the chunks of the level its output lives on
-static void rag_wgrad_slots(avc_plan* p, LayerP& L, const avc_plan::RagLevel& yl) {
-    L.rwg_nsplit = avc_rwg_nsplit(L.Cin, L.Cout, yl.nchunks);
-    if (L.rwg_nsplit > 1) L.rwg_slab = p->alloc((long)L.rwg_nsplit * avc_rwg_slot_floats(L.Cin, L.Cout, L.KS));
+// (a stacked layer -- the content encoder's two heads, the decoder's 2n affine Linears -- is nsrc tensors of `rows` output channels, each a
+// job of its own; every other layer has nsrc = 1 and rows = Cout)
+static void rag_wgrad_slots(avc_plan* p, LayerP& L, int nchunks) {
+    L.rwg_nsplit = avc_rwg_nsplit(L.Cin, L.rows, nchunks);
+    if (L.rwg_nsplit > 1) L.rwg_slab = p->alloc((long)L.nsrc * L.rwg_nsplit * avc_rwg_slot_floats(L.Cin, L.rows, L.KS));
 }
+static void rag_wgrad_slots(avc_plan* p, LayerP& L, const avc_plan::RagLevel& yl) { rag_wgrad_slots(p, L, yl.nchunks); }
 
 // flags: what avc_plan_flags reports, minus INFERENCE | RAGGED.  With AVC_PLAN_FANOUT the decoder runs over N samples mapped onto the B
 // sources by src_of; without it over the B sources themselves.
@@ -2368,6 +2388,17 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
         p->named["enc_y0"] = e.h0;
         p->named["enc_st0"] = e.st0;
         rag_name_levels(p, "enc", e.n, {{"y1", e.y1}, {"y2", e.y2}, {"st1", e.st1}, {"st2", e.st2}});
+        if (flags & AVC_PLAN_PART_GRADS) {   // avc_content_backward_ragged_params: chunk tables, conv1's own dy rows, the split-K slots
+            for (avc_plan::RagLevel& l : p->rl_enc) rag_chunks(p, l);
+            p->rag_dy1 = p->alloc(C * sumT);
+            for (int id : e.bank) rag_wgrad_slots(p, p->layers[id], p->rl_enc[0]);
+            rag_wgrad_slots(p, p->layers[e.in_conv], p->rl_enc[0]);
+            for (int l = 0; l < e.n; ++l) {
+                rag_wgrad_slots(p, p->layers[e.c1[l]], p->rl_enc[l]);
+                rag_wgrad_slots(p, p->layers[e.c2[l]], p->rl_enc[l + 1]);
+            }
+            rag_wgrad_slots(p, p->layers[e.heads], p->rl_enc[e.n]);
+        }
     }
     if (do_dec) {   // the in_conv stage lives on the B sources' level, everything above on the Nd outputs' levels
         d.cond = p->alloc((long)Nd * 2 * d.n * 2 * Cd);
@@ -2397,6 +2428,17 @@ static int rag_plan_create(const avc_model_cfg* cfg, int B, const int* T, const 
         p->named["dec_y0"] = d.y0;
         p->named["dec_st0"] = d.st0;
         rag_name_levels(p, "dec", d.n, {{"y1", d.y1}, {"a1", d.a1}, {"y2", d.y2}, {"st1", d.st1}, {"st2", d.st2}});
+        if (flags & AVC_PLAN_PART_GRADS) {   // avc_decoder_backward_ragged_params: chunk tables, conv1's own dy rows, the split-K slots
+            for (avc_plan::RagLevel& l : p->rl_dec) rag_chunks(p, l);
+            p->rag_dy1 = p->alloc(Cd * top);
+            rag_wgrad_slots(p, p->layers[d.in_conv], p->rl_dec[0]);
+            for (int l = 0; l < d.n; ++l) {   // (conv2's dy lies as its own [C up][T_l] output rows: level l for both convs)
+                rag_wgrad_slots(p, p->layers[d.c1[l]], p->rl_dec[l]);
+                rag_wgrad_slots(p, p->layers[d.c2[l]], p->rl_dec[l]);
+            }
+            rag_wgrad_slots(p, p->layers[d.affine], avc_cdiv(Nd, 32));   // (strided jobs: the Nd samples are the frames)
+            rag_wgrad_slots(p, p->layers[d.out_conv], p->rl_dec[d.n]);
+        }
     }
     p->rag_tab = p->alloc((long)p->rag_host.size());
     plan_init_streams(p);
@@ -2760,27 +2802,40 @@ struct RagWg {
     std::vector<RagWgJob> jobs;
     std::vector<RagWgRed> reds;
     // x: blocks of xC channels on level xl, the layer reads Cin of them from xc0; dy: blocks of dyC channels on level yl, Cout from dyc0
+    // k: which tensor of a stacked layer (its L.rows output channels lie at dyc0 + k L.rows of the dy blocks); every other layer: k = 0
     void add(const LayerP& L, const float* x, int xC, int xc0, const avc_plan::RagLevel& xl, const float* dy, int dyC, int dyc0,
-             const avc_plan::RagLevel& yl) {
+             const avc_plan::RagLevel& yl, int k = 0) {
         if (!grads) return;
         RagWgJob j;
         memset(&j, 0, sizeof(j));
         j.x = x; j.dy = dy;
         j.Tin = tab + xl.dT; j.offin = tab + xl.doff; j.Tout = tab + yl.dT; j.offout = tab + yl.doff; j.chunk = tab + yl.dchunk;
-        j.xC = xC; j.xc0 = xc0; j.dyC = dyC; j.dyc0 = dyc0;
-        j.Cin = L.Cin; j.Cout = L.Cout; j.KS = L.KS; j.stride = L.stride;
-        j.nchunks = yl.nchunks; j.nsplit = L.rwg_nsplit;
-        j.slot_floats = avc_rwg_slot_floats(L.Cin, L.Cout, L.KS);
-        float* dw = grads + p->params[L.w[0]].off;
-        float* db = grads + p->params[L.b[0]].off;
-        j.out = j.nsplit > 1 ? ws + L.rwg_slab : dw;
+        j.xC = xC; j.xc0 = xc0; j.dyC = dyC; j.dyc0 = dyc0 + k * L.rows;
+        j.Cin = L.Cin; j.Cout = L.rows; j.KS = L.KS; j.stride = L.stride;
+        j.nchunks = yl.nchunks;
+        finish(j, L, k);
+    }
+    // tensor k of a stacked Linear over N rows read through strides (RagWgJob::strided): x(n, ci) = x[n sxn + ci sxc], dy likewise
+    void add_strided(const LayerP& L, int k, const float* x, long sxn, long sxc, const float* dy, long syn, long syc, int N) {
+        if (!grads) return;
+        RagWgJob j;
+        avc_rwg_strided_job(j, x, sxn, sxc, dy, syn, syc, N, L.Cin, L.rows);
+        finish(j, L, k);
+    }
+    // where the job's result goes: straight into grads, or into the layer's slots and through the reduce launch
+    void finish(RagWgJob& j, const LayerP& L, int k) {
+        j.nsplit = L.rwg_nsplit;
+        j.slot_floats = avc_rwg_slot_floats(L.Cin, L.rows, L.KS);
+        float* dw = grads + p->params[L.w[k]].off;
+        float* db = grads + p->params[L.b[k]].off;
+        j.out = j.nsplit > 1 ? ws + L.rwg_slab + (long)k * j.nsplit * j.slot_floats : dw;
         j.db = db;
         jobs.push_back(j);
         if (j.nsplit > 1) {
             RagWgRed r;
             memset(&r, 0, sizeof(r));
             r.slab = j.out; r.dw = dw; r.db = db;
-            r.slot_floats = j.slot_floats; r.n_w = (long)L.Cout * L.Cin * L.KS; r.n_b = L.Cout; r.nsplit = j.nsplit;
+            r.slot_floats = j.slot_floats; r.n_w = (long)L.rows * L.Cin * L.KS; r.n_b = L.rows; r.nsplit = j.nsplit;
             reds.push_back(r);
         }
     }
@@ -2886,16 +2941,24 @@ extern "C" int avc_backward_ragged(const avc_plan* p, const float* params, const
 //   d_muls -> heads^T -> per block, last to first: IN-bwd(y2) -> conv2^T -> IN-bwd(y1) -> conv1^T with the pool / identity adjoint of the
 //   residual path in its epilogue join -> IN-bwd(y0) -> in_conv input gradient (d(cat), masked by the bank's activations) -> the nb + 1 terms
 //   of d(x), summed through the residual join of consecutive launches into ws["d_x"] in x's own [sum T][M] layout (as rag_backward_impl).
-static int rag_content_backward_impl(const avc_plan* p, const float* d_muls, float* ws, hipStream_t s) {
+// avc_content_backward_ragged_params only (grads == NULL: the frozen pass records nothing and launches what it launched): the RagWg jobs
+// of rag_backward_impl.  conv1's dy of a block goes to the plan's extra row set dy1 instead of dyA, so conv2's dy (dyA) is still live
+// behind it and the block's two jobs share ONE launch (the alternative, launching conv2's job before the second InstanceNorm backward,
+// costs n more launches); the two heads' jobs read the caller's d_muls and ride in the first block's launch.
+static int rag_content_backward_impl(const avc_plan* p, const float* d_muls, float* ws, hipStream_t s, float* grads = nullptr) {
     const int B = p->B;
     const EncNet& e = p->enc;
     const std::vector<avc_plan::RagLevel>& lv = p->rl_enc;
     const int C = e.c.c_h;
     RagBwd c(p, ws, s, e.slope);
+    RagWg w{p, ws, grads, c.tab, s, {}, {}};
+    float* dy1 = grads ? ws + p->rag_dy1 : c.dyA;
     {   // G_n = heads^T(d_muls): the caller's [2 c_out][Tz_s] blocks
         ConvArgs a = rag_dgrad(c, p->layers[e.heads], d_muls, lv[e.n], 2 * e.c.c_out, c.gA, lv[e.n], C);
         RUN(c.launch(a));
     }
+    for (int k = 0; k < 2; ++k)   // mean_layer, std_layer: rows [k c_out, (k + 1) c_out) of the d_muls blocks
+        w.add(p->layers[e.heads], ws + e.out[e.n], C, 0, lv[e.n], d_muls, 2 * e.c.c_out, 0, lv[e.n], k);
     for (int l = e.n - 1; l >= 0; --l) {
         const int sub = e.c.subsample[l];
         RUN(rag_in_bwd(c, B, C, c.gA, e.y2[l], e.st2[l], lv[l + 1], c.dyA));
@@ -2903,16 +2966,27 @@ static int rag_content_backward_impl(const avc_plan* p, const float* d_muls, flo
             ConvArgs a = rag_dgrad(c, p->layers[e.c2[l]], c.dyA, lv[l + 1], C, c.dyB, lv[l], C);
             RUN(c.launch(a));
         }
-        RUN(rag_in_bwd(c, B, C, c.dyB, e.y1[l], e.st1[l], lv[l], c.dyA));
+        RUN(rag_in_bwd(c, B, C, c.dyB, e.y1[l], e.st1[l], lv[l], dy1));
+        // dW(conv2) = d(y2) x a1, dW(conv1) = d(y1) x out_l: one launch
+        w.add(p->layers[e.c2[l]], ws + e.a1[l], C, 0, lv[l], c.dyA, C, 0, lv[l + 1]);
+        w.add(p->layers[e.c1[l]], ws + e.out[l], C, 0, lv[l], dy1, C, 0, lv[l]);
+        RUN(w.launch());
         {   // G_l = conv1^T(d(y1)) + pool^T(G_{l+1})
-            ConvArgs a = rag_dgrad(c, p->layers[e.c1[l]], c.dyA, lv[l], C, c.gC, lv[l], C);
+            ConvArgs a = rag_dgrad(c, p->layers[e.c1[l]], dy1, lv[l], C, c.gC, lv[l], C);
             set_rag_res(a, c.tab, c.gA, sub > 1 ? AVC_RES_POOLT : AVC_RES_IDENTITY, lv[l + 1], C);
             RUN(c.launch(a));
         }
         std::swap(c.gA, c.gC);
     }
     RUN(rag_in_bwd(c, B, C, c.gA, e.h0, e.st0, lv[0], c.dyA));
-    return rag_enc_input_tail(c, e, lv[0], c.dyA);
+    RUN(rag_enc_input_tail(c, e, lv[0], c.dyA));
+    if (!grads) return 0;
+    // as the speaker pass: dW(in_conv) = d(y0) x cat, dW(bank g) = its slice of d(cat) x the M pass-through rows of cat; then the slots -> grads
+    w.add(p->layers[e.in_conv], ws + e.cat, e.CC, 0, lv[0], c.dyA, C, 0, lv[0]);
+    for (int g = 0; g < e.nb; ++g)
+        w.add(p->layers[e.bank[g]], ws + e.cat, e.CC, e.nb * e.c.c_bank, lv[0], ws + e.dcat, e.CC, g * e.c.c_bank, lv[0]);
+    RUN(w.launch());
+    return w.reduce();
 }
 
 extern "C" int avc_content_backward_ragged(const avc_plan* p, const float* params, const float* x, const float* d_muls, float* ws, void* stream) {
@@ -2926,6 +3000,21 @@ extern "C" int avc_content_backward_ragged(const avc_plan* p, const float* param
     return rag_content_backward_impl(p, d_muls, ws, (hipStream_t)stream);
 }
 
+// The ragged content backward WITH parameter gradients: rag_content_backward_impl plus one ragged weight-gradient launch per block (the
+// heads in the first), one for the in_conv and the bank, and one reduce launch: n + 2 launches on top of the frozen pass.  Overwrites
+// exactly the content encoder's tensors of `grads`.
+extern "C" int avc_content_backward_ragged_params(const avc_plan* p, const float* params, const float* x, const float* d_muls, float* grads,
+                                                  float* ws, void* stream) {
+    if (!p || !params || !x || !d_muls || !grads || !ws)
+        return fail(-1, "avc_content_backward_ragged_params: null argument (pass the avc_plan_create_ragged_content_param_grads plan, params, x and workspace of the avc_forward_ragged this pass follows, d_muls and grads)");
+    if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_CONTENT_ONLY) || !(p->flags & AVC_PLAN_INPUT_GRADS) || !(p->flags & AVC_PLAN_PART_GRADS))
+        return fail(-8, "avc_content_backward_ragged_params: the plan was not created by avc_plan_create_ragged_content_param_grads");
+    if (p->compute != AVC_COMPUTE_F32)
+        return fail(-8, "avc_content_backward_ragged_params: the avc_plan_create_ragged_content_param_grads plan computes with bf16 operand rounding, a forward-only model; "
+                        "gradients need fp32 (avc_plan_set_compute_dtype(p, 0)) or a uniform plan");
+    return rag_content_backward_impl(p, d_muls, ws, (hipStream_t)stream, grads);
+}
+
 // The backward pass of a plan of avc_plan_create_ragged_decoder_grads: d(loss)/d(z) and d(loss)/d(emb) from d(loss)/d(dec), parameters
 // frozen.  One branch on the caller's stream, the uniform decoder chain of avc_backward_impl minus every weight gradient:
 //   d_dec -> out_conv^T -> per block, last to first: AdaIN-bwd(y2) (planar store where the block upsamples: the rows leave as the conv's
@@ -2933,16 +3022,26 @@ extern "C" int avc_content_backward_ragged(const avc_plan* p, const float* param
 //   in its epilogue join -> IN-bwd(y0) -> in_conv^T into ws["d_z"] ([c_in][Tz_s] blocks) -> d(emb) = W_affine^T d(cond), one uniform
 //   input-gradient launch over N columns that stores row-major [N][c_cond] into ws["d_emb"].
 // 1 + 4 n + 2 + 1 launches (28 for the stock 6 blocks): every AdaIN backward writes its [N][2 C] slice of d(cond) once, nothing is zeroed.
-static int rag_decoder_backward_impl(const avc_plan* p, const float* d_dec, float* ws, hipStream_t s) {
+// avc_decoder_backward_ragged_params only (grads == NULL: the frozen pass records nothing, launches what it launched and reads neither z
+// nor emb): the RagWg jobs, with conv1's dy in the plan's extra row set as in rag_content_backward_impl.  out_conv's job reads the caller's
+// d_dec and rides in the last block's launch; conv2's dy is already planar -- the conv's own [C up][T_l] output rows -- so its job is a
+// packed one on level l; the in_conv's job (KS = 1) reads the caller's latent blocks in place; the 2n affine Linears are 2n STRIDED jobs
+// (dy = the [N][2 C] slice of frame-major d(cond), x = the caller's emb through (seb, sec)) in the in_conv's launch.
+static int rag_decoder_backward_impl(const avc_plan* p, const float* d_dec, float* ws, hipStream_t s, float* grads = nullptr, const float* z = nullptr,
+                                     int zc = 0, const float* emb = nullptr, long seb = 0, long sec = 0) {
     const int N = p->Nd;
     const DecNet& d = p->dec;
     const std::vector<avc_plan::RagLevel>& lv = p->rl_dec;
     const int C = d.c.c_h, Cz = d.c.c_in;
+    const long csb = (long)2 * d.n * 2 * C;
     RagBwd c(p, ws, s, d.slope);
+    RagWg w{p, ws, grads, c.tab, s, {}, {}};
+    float* dy1 = grads ? ws + p->rag_dy1 : c.dyA;
     {   // G_n = out_conv^T(d_dec): the caller's [M][T''_j] blocks
         ConvArgs a = rag_dgrad(c, p->layers[d.out_conv], d_dec, lv[d.n], p->M, c.gA, lv[d.n], C);
         RUN(c.launch(a));
     }
+    w.add(p->layers[d.out_conv], ws + d.out[d.n], C, 0, lv[d.n], d_dec, p->M, 0, lv[d.n]);
     for (int l = d.n - 1; l >= 0; --l) {
         const int up = d.c.upsample[l];
         RUN(rag_in_bwd(c, N, C, c.gA, d.y2[l], d.st2[l], lv[l + 1], c.dyA, (2 * l + 1) * 2 * C, up));
@@ -2950,9 +3049,13 @@ static int rag_decoder_backward_impl(const avc_plan* p, const float* d_dec, floa
             ConvArgs a = rag_dgrad(c, p->layers[d.c2[l]], c.dyA, lv[l], C * up, c.dyB, lv[l], C);
             RUN(c.launch(a));
         }
-        RUN(rag_in_bwd(c, N, C, c.dyB, d.y1[l], d.st1[l], lv[l], c.dyA, (2 * l) * 2 * C, 1));
+        RUN(rag_in_bwd(c, N, C, c.dyB, d.y1[l], d.st1[l], lv[l], dy1, (2 * l) * 2 * C, 1));
+        // dW(conv2) = d(y2) x a1 (both on level l), dW(conv1) = d(y1) x out_l: one launch
+        w.add(p->layers[d.c2[l]], ws + d.a1[l], C, 0, lv[l], c.dyA, C * up, 0, lv[l]);
+        w.add(p->layers[d.c1[l]], ws + d.out[l], C, 0, lv[l], dy1, C, 0, lv[l]);
+        RUN(w.launch());
         {   // G_l = conv1^T(d(y1)) + up^T(G_{l+1})
-            ConvArgs a = rag_dgrad(c, p->layers[d.c1[l]], c.dyA, lv[l], C, c.gC, lv[l], C);
+            ConvArgs a = rag_dgrad(c, p->layers[d.c1[l]], dy1, lv[l], C, c.gC, lv[l], C);
             set_rag_res(a, c.tab, c.gA, up > 1 ? AVC_RES_UPT : AVC_RES_IDENTITY, lv[l + 1], C);
             RUN(c.launch(a));
         }
@@ -2965,11 +3068,15 @@ static int rag_decoder_backward_impl(const avc_plan* p, const float* d_dec, floa
     }
     {   // d(emb)[b][i] = sum_o W[o][i] d(cond)[b][o]: the stacked affine layer's input gradient, "frames" = the N samples (d(cond) read with
         // channel stride 1, frame stride csb), stored row-major through the output strides -- the mirror image of the forward affine launch
-        const long csb = (long)2 * d.n * 2 * C;
         ConvArgs a = mk_dgrad(c.slope, p->layers[d.affine], ws, ws + d.dcond, 0, 1, (int)csb, 1, 1, N, N, ws + p->demb_rm, 0, 1, d.c.c_cond);
         RUN(avc_launch_conv(a, s, 0, p->tun));
     }
-    return 0;
+    if (!grads) return 0;
+    w.add(p->layers[d.in_conv], z, zc, 0, lv[0], c.dyA, C, 0, lv[0]);
+    for (int k = 0; k < 2 * d.n; ++k)   // affine Linear k: beta rows, then gamma rows, as its AdaIN backward left them in d(cond)
+        w.add_strided(p->layers[d.affine], k, emb, seb, sec, ws + d.dcond + (long)k * 2 * C, csb, 1, N);
+    RUN(w.launch());
+    return w.reduce();
 }
 
 // z / zc / emb / seb / sec: what the avc_decoder_forward_ragged this pass follows was given (the frozen-parameter pass reads the saved rows,
@@ -2995,4 +3102,25 @@ extern "C" int avc_decoder_backward_ragged(const avc_plan* p, const float* param
         return fail(-1, "avc_decoder_backward_ragged: zc is too small: a latent block has at least c_in rows");
     if (int rc = check_row_strides("avc_decoder_backward_ragged", "emb", p->Nd, p->cfg.dec.c_cond, seb, sec)) return rc;
     return rag_decoder_backward_impl(p, d_dec, ws, (hipStream_t)stream);
+}
+
+// The ragged decoder backward WITH parameter gradients: rag_decoder_backward_impl plus one ragged weight-gradient launch per block (out_conv
+// in the first), one for the in_conv and the 2n affine Linears, and one reduce launch: n + 2 launches on top of the frozen pass.  z and emb
+// are READ here (the in_conv's and the affine Linears' forward inputs): they must be the forward's.  Overwrites exactly the decoder's
+// tensors of `grads`.
+extern "C" int avc_decoder_backward_ragged_params(const avc_plan* p, const float* params, const float* z, int zc, const float* emb, long seb, long sec,
+                                                  const float* d_dec, float* grads, float* ws, void* stream) {
+    if (!p || !params || !z || !emb || !d_dec || !grads || !ws)
+        return fail(-1, "avc_decoder_backward_ragged_params: null argument (pass the avc_plan_create_ragged_decoder_param_grads plan, params, z, emb and workspace of the "
+                        "avc_decoder_forward_ragged this pass follows, d_dec and grads)");
+    if (!(p->flags & AVC_PLAN_RAGGED) || !(p->flags & AVC_PLAN_DECODER_ONLY) || !(p->flags & AVC_PLAN_INPUT_GRADS) || !(p->flags & AVC_PLAN_PART_GRADS) ||
+        (p->flags & AVC_PLAN_FANOUT))
+        return fail(-8, "avc_decoder_backward_ragged_params: the plan was not created by avc_plan_create_ragged_decoder_param_grads");
+    if (p->compute != AVC_COMPUTE_F32)
+        return fail(-8, "avc_decoder_backward_ragged_params: the avc_plan_create_ragged_decoder_param_grads plan computes with bf16 operand rounding, a forward-only model; "
+                        "gradients need fp32 (avc_plan_set_compute_dtype(p, 0)) or a uniform plan (avc_decoder_backward)");
+    if (zc < p->cfg.dec.c_in)
+        return fail(-1, "avc_decoder_backward_ragged_params: zc is too small: a latent block has at least c_in rows");
+    if (int rc = check_row_strides("avc_decoder_backward_ragged_params", "emb", p->Nd, p->cfg.dec.c_cond, seb, sec)) return rc;
+    return rag_decoder_backward_impl(p, d_dec, ws, (hipStream_t)stream, grads, z, zc, emb, seb, sec);
 }

@@ -370,7 +370,14 @@ class RaggedPlan:
     them into the flat buffer ``grads`` and leaves ``d_x_cond(ws)``; ``backward`` stays the frozen pass.  (A mode of its own, like
     "decode_ig": ``mode="speaker", input_grads=True`` keeps its plan, workspace size and launches.)  ``buffer()`` names of the saved rows: "dec_y0", "dec_y1_<l>", "dec_a1_<l>", "dec_y2_<l>", their statistics
     "dec_st0", "dec_st1_<l>", "dec_st2_<l>", and "cond" / "d_cond".  (``mode="decode", input_grads=True`` keeps raising: fan-out plans,
-    with their free ``src_of``, are forward only.)"""
+    with their free ``src_of``, are forward only.)
+
+    modes "encode_pg" (avc_plan_create_ragged_content_param_grads) and "decode_pg" (avc_plan_create_ragged_decoder_param_grads;
+    ``input_grads`` is implied): the ``mode="encode", input_grads=True`` / "decode_ig" plans whose backward pass can also compute the
+    network's PARAMETER gradients: ``backward_content_params(params, x, d_muls, grads, ws)`` / ``backward_decoder_params(params, z, zc,
+    emb, d_dec, grads, ws)`` write them into the flat buffer ``grads`` and leave ``d_x(ws)`` / ``d_z(ws)`` and ``d_emb(ws)``;
+    ``backward_content`` / ``backward_decoder`` stay the frozen passes.  Forwards and frozen passes are bit-identical to the older plans';
+    those keep their workspace sizes and launches."""
 
     MODES = {"pairs": 0, "speaker": _lib.PLAN_SPEAKER_ONLY, "emb": _lib.PLAN_EMB_INPUT}
     FAN_MODES = {"fanout": 0, "encode": _lib.PLAN_CONTENT_ONLY, "decode": _lib.PLAN_DECODER_ONLY}
@@ -384,14 +391,16 @@ class RaggedPlan:
              "encode": ("T", False, (_FAN, FAN_MODES["encode"]), ("avc_plan_create_ragged_content_grads", 0)),
              "decode": ("T", True, (_FAN, FAN_MODES["decode"]), None),
              "decode_ig": ("T", False, None, ("avc_plan_create_ragged_decoder_grads", 0)),
-             "speaker_pg": ("T_cond", False, None, ("avc_plan_create_ragged_speaker_grads", 0))}
+             "speaker_pg": ("T_cond", False, None, ("avc_plan_create_ragged_speaker_grads", 0)),
+             "encode_pg": ("T", False, None, ("avc_plan_create_ragged_content_param_grads", 0)),
+             "decode_pg": ("T", False, None, ("avc_plan_create_ragged_decoder_param_grads", 0))}
 
     def __init__(self, config, T, T_cond=None, lib=None, compute_dtype="fp32", device=None, tuning=None, mode="pairs", input_grads=False,
                  src_of=None):
         self.lib = lib if lib is not None else _lib.load()
         self.cfg = cfg_from_dict(config)
         if mode not in self.KINDS:
-            raise ValueError(f"mode must be one of {sorted(self.MODES) + sorted(self.FAN_MODES) + ['decode_ig', 'speaker_pg']}, got {mode!r}")
+            raise ValueError(f"mode must be one of {sorted(self.MODES) + sorted(self.FAN_MODES) + ['decode_ig', 'speaker_pg', 'encode_pg', 'decode_pg']}, got {mode!r}")
         lengths, takes_src_of, plain, with_grads = self.KINDS[mode]
         self.mode = mode
         self.input_grads = bool(input_grads) or plain is None
@@ -426,7 +435,7 @@ class RaggedPlan:
             raise ValueError("ragged plans compute in fp32 or bf16 (operand rounding: the pair-storage engine takes uniform shapes)")
         h = ctypes.c_void_p()
         tun = _lib.make_tuning(self.lib, tuning)
-        self.N = len(self.src_of) if self.src_of is not None else (0 if mode == "encode" else self.B)
+        self.N = len(self.src_of) if self.src_of is not None else (0 if mode in ("encode", "encode_pg") else self.B)
         lens = _ints(self.T)
         args = {"avc_plan_create_ragged": (lens, _ints(self.T_cond)), self._EX: (lens, _ints(self.T_cond), flags),
                 self._FAN: (lens, self.N, _ints(self.src_of), flags)}.get(creator, (_ints(self.T_cond) if lengths == "T_cond" else lens,))
@@ -445,13 +454,13 @@ class RaggedPlan:
         self.workspace_floats = self.lib.avc_plan_workspace_floats(h)
         self.num_params, self.param_info = _param_info(self.lib, h)
         self.out_len, self.out_off = [], []
-        if mode not in ("speaker", "speaker_pg", "encode"):
+        if mode not in ("speaker", "speaker_pg", "encode", "encode_pg"):
             lens, offs = (ctypes.c_int * self.N)(), (ctypes.c_long * self.N)()
             if self.lib.avc_plan_ragged_out(h, lens, offs) != 0:
                 raise RuntimeError(self.lib.avc_last_error().decode())
             self.out_len, self.out_off = list(lens), list(offs)
         self.lat_len, self.lat_off = [], []   # per SOURCE: latent frames and the float offset of its (mu | log_sigma) block in ws["muls"]
-        if mode not in ("speaker", "speaker_pg", "decode", "decode_ig") and hasattr(self.lib, "avc_plan_ragged_latents"):
+        if mode not in ("speaker", "speaker_pg", "decode", "decode_ig", "decode_pg") and hasattr(self.lib, "avc_plan_ragged_latents"):
             lens, offs = (ctypes.c_int * self.B)(), (ctypes.c_long * self.B)()
             if self.lib.avc_plan_ragged_latents(h, lens, offs) != 0:
                 raise RuntimeError(self.lib.avc_last_error().decode())
@@ -474,9 +483,9 @@ class RaggedPlan:
         A "speaker" plan reads x_cond only (pass x = None)."""
         if self.mode in ("emb", "fanout"):
             raise RuntimeError(f"an {self.mode!r} plan has no speaker encoder: call forward_emb(params, x, emb, ws)")
-        if self.mode in ("decode", "decode_ig"):
+        if self.mode in ("decode", "decode_ig", "decode_pg"):
             raise RuntimeError("a 'decode' plan starts from latents: call forward_latents(params, z, zc, emb, ws)")
-        if self.mode == "encode":
+        if self.mode in ("encode", "encode_pg"):
             if x_cond is not None:
                 raise ValueError("an 'encode' plan runs the content encoder alone: forward(params, x, None, ws)")
             self._rows(x, self.T, "x")
@@ -514,7 +523,7 @@ class RaggedPlan:
         """"decode" plans: z holds the S latent blocks back to back, block s = [zc][T[s]] fp32 (frames contiguous) at float offset
         zc * sum(T[:s]); the first c_lat channels of a block are read in place.  zc = c_lat: mu-only blocks; zc = 2 c_lat: the
         ws["muls"] region of a plan with a content encoder over the same sources, passed as it is.  emb: [N, c_cond] as in ``forward_emb``."""
-        if self.mode not in ("decode", "decode_ig"):
+        if self.mode not in ("decode", "decode_ig", "decode_pg"):
             raise RuntimeError(f"forward_latents needs a plan of mode 'decode' (this one is {self.mode!r})")
         z, zc, emb = self._latents(z, zc, emb, ws)
         with _on(ws):
@@ -533,7 +542,7 @@ class RaggedPlan:
         d(loss)/d(emb) from d_dec = d(loss)/d(dec): fp32, contiguous, n_mels * sum(out_len) elements on the workspace's device, block j =
         [n_mels][out_len[j]] at element n_mels * sum(out_len[:j]) -- the layout of the workspace region ``outputs(ws)`` views.  The results
         are ``d_z(ws)`` and ``d_emb(ws)``.  No parameter gradients; two calls give identical bits."""
-        if self.mode != "decode_ig":
+        if self.mode not in ("decode_ig", "decode_pg"):
             raise RuntimeError("backward_decoder needs RaggedPlan(mode='decode_ig') "
                                f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
         z, zc, emb = self._latents(z, zc, emb, ws)
@@ -592,13 +601,44 @@ class RaggedPlan:
         d_muls = d(loss)/d(mu | log_sigma): fp32, contiguous, 2 c_lat * sum(lat_len) elements on the workspace's device, block s =
         [2 c_lat][lat_len[s]] (mu rows, then log_sigma rows) at element 2 c_lat * sum(lat_len[:s]) -- the layout of the workspace region
         ``latents(ws)`` views.  The result is ``d_x(ws)``.  No parameter gradients; two calls give identical bits."""
-        if not (self.mode == "encode" and self.input_grads):
+        if not (self.mode in ("encode", "encode_pg") and self.input_grads):
             raise RuntimeError("backward_content needs RaggedPlan(mode='encode', input_grads=True) "
                                f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
         self._rows(x, self.T, "x")
         _packed(d_muls, 2 * self.c_lat * sum(self.lat_len), "d_muls", " (the layout of the plan's latent blocks)", ws)
         with _on(ws):
             self._chk(self.lib.avc_content_backward_ragged(self.h, _ptr(params), _ptr(x), _ptr(d_muls), _ptr(ws), _stream(ws)))
+
+    def backward_content_params(self, params, x, d_muls, grads, ws):
+        """``mode="encode_pg"`` plans, after ``forward(params, x, None, ws)`` in the same workspace: ``backward_content`` plus
+        d(loss)/d(parameters) of the content encoder, from the same pass (avc_content_backward_ragged_params).  ``grads``: a flat fp32
+        buffer of ``param_floats`` elements on the workspace's device; the pass overwrites every content-encoder tensor in it (weights and
+        biases) and nothing else.  ``d_x(ws)`` is what ``backward_content`` leaves there, bit for bit.  fp32 only; two calls give
+        identical bits."""
+        if self.mode != "encode_pg":
+            raise RuntimeError("backward_content_params needs RaggedPlan(mode='encode_pg') "
+                               f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
+        self._rows(x, self.T, "x")
+        _packed(d_muls, 2 * self.c_lat * sum(self.lat_len), "d_muls", " (the layout of the plan's latent blocks)", ws)
+        _packed(grads, self.param_floats, "grads", " (the flat parameter layout)", ws, at_least=True)
+        with _on(ws):
+            self._chk(self.lib.avc_content_backward_ragged_params(self.h, _ptr(params), _ptr(x), _ptr(d_muls), _ptr(grads), _ptr(ws), _stream(ws)))
+
+    def backward_decoder_params(self, params, z, zc, emb, d_dec, grads, ws):
+        """``mode="decode_pg"`` plans, after ``forward_latents(params, z, zc, emb, ws)`` in the same workspace: ``backward_decoder`` plus
+        d(loss)/d(parameters) of the decoder, from the same pass (avc_decoder_backward_ragged_params).  z, zc and emb must be the
+        forward's: the in_conv's and the AdaIN affine Linears' weight gradients READ them (emb in place through its strides, an expanded
+        single voice included).  ``grads`` as for ``backward_content_params``: every decoder tensor is overwritten, nothing else.
+        ``d_z(ws)`` and ``d_emb(ws)`` are what ``backward_decoder`` leaves there, bit for bit.  fp32 only; two calls give identical bits."""
+        if self.mode != "decode_pg":
+            raise RuntimeError("backward_decoder_params needs RaggedPlan(mode='decode_pg') "
+                               f"(this one: mode={self.mode!r}, input_grads={self.input_grads})")
+        z, zc, emb = self._latents(z, zc, emb, ws)
+        _packed(d_dec, self.n_mels * sum(self.out_len), "d_dec", " (the layout of the plan's output blocks)", ws)
+        _packed(grads, self.param_floats, "grads", " (the flat parameter layout)", ws, at_least=True)
+        with _on(ws):
+            self._chk(self.lib.avc_decoder_backward_ragged_params(self.h, _ptr(params), _ptr(z), zc, _ptr(emb), emb.stride(0), emb.stride(1),
+                                                                  _ptr(d_dec), _ptr(grads), _ptr(ws), _stream(ws)))
 
     def d_x(self, ws):
         """[sum T, M] view of d(loss)/d(x) in the workspace (after ``backward_content``): rows of frames, utterance after utterance"""

@@ -425,6 +425,54 @@ class _RaggedDecoderFunction(_RaggedFunction):
         return None, ws[o:o + plan.c_lat * sum(plan.T)].clone(), plan.d_emb(ws).clone(), None
 
 
+class _RaggedContentParamFunction(_RaggedFunction):
+    """``AE.content_encoder_ragged(param_grads=True)`` (an "encode_pg" RaggedPlan): ``_RaggedContentFunction`` with the content encoder's
+    parameters as inputs of the function -- their gradients and the packed input gradient come from ONE ragged backward pass
+    (``avc_content_backward_ragged_params``), the pattern of ``_RaggedSpeakerParamFunction``."""
+
+    @staticmethod
+    def forward(ctx, ae, x, T, *params):
+        plan, ws = _RaggedFunction._begin(ctx, ae, "encode_pg", T, (), x.device)
+        plan.forward(ae._flat, x, None, ws)
+        ctx.save_for_backward(x)
+        o = plan.lat_off[0]
+        return ws[o:o + 2 * plan.c_lat * sum(plan.lat_len)].clone()
+
+    @staticmethod
+    def backward(ctx, d_muls):
+        _PartFunction._check(ctx)
+        x, = ctx.saved_tensors
+        g = torch.empty_like(ctx.ae._flat)
+        ctx.plan.backward_content_params(ctx.ae._flat, x, d_muls.float().contiguous(), g, ctx.ws)
+        dx = ctx.plan.d_x(ctx.ws).clone() if ctx.needs_input_grad[1] else None
+        return (None, dx, None) + _PartFunction._grads(ctx, g, "content")
+
+
+class _RaggedDecoderParamFunction(_RaggedFunction):
+    """``AE.decoder_ragged(param_grads=True)`` (a "decode_pg" RaggedPlan): ``_RaggedDecoderFunction`` with the decoder's parameters as inputs
+    of the function; one ragged backward pass (``avc_decoder_backward_ragged_params``) gives their gradients, d(z) and d(emb)."""
+
+    @staticmethod
+    def forward(ctx, ae, z, e, Tz, *params):
+        plan, ws = _RaggedFunction._begin(ctx, ae, "decode_pg", Tz, (), z.device)
+        plan.forward_latents(ae._flat, z, plan.c_lat, e, ws)
+        ctx.save_for_backward(z, e)
+        o = plan.out_off[0]
+        return ws[o:o + plan.n_mels * sum(plan.out_len)].clone()
+
+    @staticmethod
+    def backward(ctx, d_dec):
+        _PartFunction._check(ctx)
+        z, e = ctx.saved_tensors
+        plan, ws = ctx.plan, ctx.ws
+        g = torch.empty_like(ctx.ae._flat)
+        plan.backward_decoder_params(ctx.ae._flat, z, plan.c_lat, e, d_dec.float().contiguous(), g, ws)
+        o = plan.buffer("d_z")
+        dz = ws[o:o + plan.c_lat * sum(plan.T)].clone() if ctx.needs_input_grad[1] else None
+        de = plan.d_emb(ws).clone() if ctx.needs_input_grad[2] else None
+        return (None, dz, de, None) + _PartFunction._grads(ctx, g, "decoder")
+
+
 class _ContentFunction(_PartFunction):
     """ContentEncoder.forward (model.py:301-323) with autograd; x gets its gradient when it requires one (a plan with
     AVC_PLAN_INPUT_GRADS)."""
@@ -659,8 +707,8 @@ class AE(nn.Module):
 
     def _ragged_plan(self, mode, T, Tc, src_of=None):
         """(RaggedPlan, pooled workspace) for a tuple of lengths; a few most recent plans of all modes are kept.  modes "speaker_ig",
-        "encode_ig", "decode_ig" (the speaker / content / decoder plan with input gradients) and "speaker_pg" (the speaker plan whose
-        backward also computes its parameter gradients) return (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
+        "encode_ig", "decode_ig" (the speaker / content / decoder plan with input gradients) and "speaker_pg", "encode_pg", "decode_pg"
+        (the plans whose backward also computes their network's parameter gradients) return (RaggedPlan, _Entry) instead: such a plan owns its workspace, which holds the saved
         activations between a forward and its backward and is never the pooled one.  ``src_of`` (a tuple; "fanout" / "decode" plans):
         the source of every output, part of the key."""
         from .engine import RaggedPlan
@@ -670,9 +718,10 @@ class AE(nn.Module):
         if hit is None:
             # compute_dtype "bf16" -> "bf16r" here: the pair-STORAGE engine takes uniform shapes only; ragged plans round the operands of
             # the matrix products to bf16 on fp32 storage (engine.RaggedPlan).  The mode that ran is reported in `last_ragged_compute`.
-            ig = mode in ("speaker_ig", "encode_ig", "decode_ig", "speaker_pg")
+            ig = mode in ("speaker_ig", "encode_ig", "decode_ig", "speaker_pg", "encode_pg", "decode_pg")
             plan = RaggedPlan(self.config, T, Tc, lib=self._lib, compute_dtype="bf16r" if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")) else "fp32", device=dev,
-                              tuning=self._tuning, mode=mode[:-3] if (ig and mode not in ("decode_ig", "speaker_pg")) else mode, input_grads=ig, src_of=src_of)
+                              tuning=self._tuning, mode=mode[:-3] if (ig and mode not in ("decode_ig", "speaker_pg", "encode_pg", "decode_pg")) else mode,
+                              input_grads=ig, src_of=src_of)
             if [(o, n) for o, n, _ in plan.param_info] != [(o, n) for o, n, _ in self._layout]:
                 raise RuntimeError("flat parameter layout of the C plan differs from the module's")
             hit = self._ragged[key] = (plan, _Entry(plan, torch.zeros(plan.workspace_floats, dtype=torch.float32, device=dev)) if ig else None)
@@ -799,7 +848,15 @@ class AE(nn.Module):
         plan.forward(self._flat, x, None, ws)
         return [mu.clone() for mu in plan.latents(ws)[0]]
 
-    def content_encoder_ragged(self, xs):
+    @staticmethod
+    def _latent_views(muls, plan):
+        """(list of mu, list of log_sigma) [c_lat, Tz_s] views of the packed (mu | log_sigma) blocks a ragged content function returns"""
+        c, base = plan.c_lat, plan.lat_off[0]
+        mu = [muls[o - base:o - base + c * n].view(c, n) for o, n in zip(plan.lat_off, plan.lat_len)]
+        ls = [muls[o - base + c * n:o - base + 2 * c * n].view(c, n) for o, n in zip(plan.lat_off, plan.lat_len)]
+        return mu, ls
+
+    def content_encoder_ragged(self, xs, param_grads=False):
         """``content_encoder`` over utterances of DIFFERENT lengths in ONE launch set: xs is a list of [T_s, M] tensors (frames as rows);
         returns (list of mu [c_lat, Tz_s], list of log_sigma [c_lat, Tz_s]), entry s == content_encoder(x_s), bit-identical to
         ``content_latents_ragged``.
@@ -810,19 +867,32 @@ class AE(nn.Module):
         (``RaggedPlan(mode="encode", input_grads=True)``); the parameters are frozen on this path (their gradients:
         ``content_encoder(x)`` on uniform shapes).  Grad plans have a workspace of their OWN (see ``get_speaker_embeddings_ragged``); a
         second grad forward of the same lengths while a backward is pending gets a private workspace.  Under ``compute_dtype: bf16`` the
-        grad path raises: use the uniform ``content_encoder(x_b)``.  Without grad the call runs the pooled forward-only "encode" plan."""
+        grad path raises: use the uniform ``content_encoder(x_b)``.  Without grad the call runs the pooled forward-only "encode" plan.
+
+        ``param_grads=True``: differentiable with respect to the content encoder's PARAMETERS as well.  With grad enabled the results
+        carry a ``grad_fn`` when a content-encoder parameter or an utterance requires grad; a backward gives every such parameter its
+        ``.grad`` (accumulated as torch accumulates; the other two networks' parameters get nothing) and every such utterance its own --
+        all from ONE ragged backward pass in fp32 (``RaggedPlan(mode="encode_pg")``, avc_content_backward_ragged_params).  When no
+        parameter requires grad the call is the default one, with its bits.  The default (False) is unchanged: it stays forward-only
+        while only parameters require grad."""
         T, x = self._ragged_rows(xs, "xs")
+        if param_grads and torch.is_grad_enabled():
+            lo, hi = self._part_index["content"]
+            params = list(self.parameters())[lo:hi]
+            if any(p.requires_grad for p in params):
+                if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")):
+                    raise RuntimeError("content_encoder_ragged: gradients through the ragged path are fp32 only, and compute_dtype is "
+                                       f"{self.compute_dtype!r} (ragged plans then run 'bf16r', a forward-only rounding model).  Use the uniform path "
+                                       "content_encoder(x_b) per utterance, or call under torch.no_grad()")
+                muls = _RaggedContentParamFunction.apply(self, x, T, *params)
+                return self._latent_views(muls, self._ragged_plan("encode_pg", T, ())[0])
         if torch.is_grad_enabled() and x.requires_grad:
             if str(self.compute_dtype).lower().startswith(("bf16", "bfloat16")):
                 raise RuntimeError("content_encoder_ragged: input gradients through the ragged path are fp32 only, and compute_dtype is "
                                    f"{self.compute_dtype!r} (ragged plans then run 'bf16r', a forward-only rounding model).  Use the uniform path "
                                    "content_encoder(x_b) per utterance, or detach the inputs")
             muls = _RaggedContentFunction.apply(self, x, T)
-            plan = self._ragged_plan("encode_ig", T, ())[0]
-            c, base = plan.c_lat, plan.lat_off[0]
-            mu = [muls[o - base:o - base + c * n].view(c, n) for o, n in zip(plan.lat_off, plan.lat_len)]
-            ls = [muls[o - base + c * n:o - base + 2 * c * n].view(c, n) for o, n in zip(plan.lat_off, plan.lat_len)]
-            return mu, ls
+            return self._latent_views(muls, self._ragged_plan("encode_ig", T, ())[0])
         plan, ws = self._ragged_plan("encode", T, ())
         plan.forward(self._flat, x, None, ws)
         mu, ls = plan.latents(ws)
@@ -850,7 +920,7 @@ class AE(nn.Module):
         plan.forward_latents(self._flat, z, self._c_lat, e, ws)
         return [o.clone() for o in plan.outputs(ws)]
 
-    def decoder_ragged(self, zs, emb):
+    def decoder_ragged(self, zs, emb, param_grads=False):
         """``decoder`` over latents of DIFFERENT lengths in ONE launch set: zs is a list of [c_lat, Tz_s] tensors, emb is [N, c_emb]
         (one row per latent) or [c_emb] / [1, c_emb] (one voice for all); returns N tensors [M, T''_j], output j == decoder(zs[j], emb_j),
         bit-identical to ``decode_ragged(zs, emb)``.
@@ -863,10 +933,23 @@ class AE(nn.Module):
         same lengths while a backward is pending gets a private workspace.  There is no ``src_of`` on the grad path: to render one latent
         in several voices pass ``[zs[j] for j in src_of]`` -- torch's autograd sums the gradients of a repeated latent.  Under
         ``compute_dtype: bf16`` the grad path raises: use the uniform ``decoder(z_b, emb_b)``.  Without grad the call is
-        ``decode_ragged(zs, emb)``."""
+        ``decode_ragged(zs, emb)``.
+
+        ``param_grads=True``: differentiable with respect to the decoder's PARAMETERS as well (fine-tuning the decoder to a voice on whole
+        utterances).  With grad enabled the results carry a ``grad_fn`` when a decoder parameter, a latent or ``emb`` requires grad; a
+        backward gives every such parameter its ``.grad`` (accumulated as torch accumulates; the other two networks' parameters get
+        nothing) and the inputs theirs -- all from ONE ragged backward pass in fp32 (``RaggedPlan(mode="decode_pg")``,
+        avc_decoder_backward_ragged_params).  When no parameter requires grad the call is the default one, with its bits.  The default
+        (False) is unchanged: it stays forward-only while only parameters require grad."""
         zs = list(zs)
+        params = ()
+        if param_grads and torch.is_grad_enabled():
+            lo, hi = self._part_index["decoder"]
+            params = list(self.parameters())[lo:hi]
+            if not any(p.requires_grad for p in params):
+                params = ()
         need = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in zs + [emb])
-        if not need:
+        if not need and not params:
             return self.decode_ragged(zs, emb)
         for z in zs:
             if not torch.is_tensor(z) or z.dim() != 2 or z.shape[0] != self._c_lat:
@@ -879,8 +962,11 @@ class AE(nn.Module):
         Tz = tuple(int(z.shape[1]) for z in zs)
         e = self._voices("decoder_ragged", emb, len(zs), "latent", detach=False)
         z = torch.cat([self._prep(z).to(dev).reshape(-1) for z in zs])   # block s = [c_lat][Tz_s], frames contiguous
-        dec = _RaggedDecoderFunction.apply(self, z, e, Tz)
-        plan = self._ragged_plan("decode_ig", Tz, ())[0]
+        if params:
+            dec = _RaggedDecoderParamFunction.apply(self, z, e, Tz, *params)
+        else:
+            dec = _RaggedDecoderFunction.apply(self, z, e, Tz)
+        plan = self._ragged_plan("decode_pg" if params else "decode_ig", Tz, ())[0]
         M, base = plan.n_mels, plan.out_off[0]
         return [dec[o - base:o - base + M * n].view(M, n) for o, n in zip(plan.out_off, plan.out_len)]
 

@@ -415,6 +415,36 @@ int avc_content_backward_ragged(const avc_plan* p, const float* params, const fl
 int avc_plan_create_ragged_decoder_grads(const avc_model_cfg* cfg, int N, const int* Tz, const avc_tuning* tuning, avc_plan** out);
 int avc_decoder_backward_ragged(const avc_plan* p, const float* params, const float* z, int zc, const float* emb, long seb, long sec,
                                 const float* d_dec, float* ws, void* stream);
+/* PARAMETER GRADIENTS OF THE RAGGED CONTENT ENCODER AND DECODER: avc_plan_create_ragged_content_param_grads(cfg, S, T, tuning, out) and
+ * avc_plan_create_ragged_decoder_param_grads(cfg, N, Tz, tuning, out) create the plans of avc_plan_create_ragged_content_grads /
+ * _decoder_grads with, on top of them, the weight gradient's K-chunk tables on every level, ONE more set of gradient rows (so that both
+ * output gradients of a block are live at once and share one weight-gradient launch) and the split-K slots of every layer that is split.
+ * avc_plan_flags additionally reports AVC_PLAN_PART_GRADS.  The forward passes (avc_forward_ragged / avc_decoder_forward_ragged) launch the
+ * same kernel instances on the same operands as those plans: ws["muls"] / ws["dec"] are bit-identical.  avc_content_backward_ragged /
+ * avc_decoder_backward_ragged work on the new plans as on the old (the frozen passes: no weight-gradient launch; ws["d_x"], ws["d_z"],
+ * ws["d_emb"] bit-identical).  The existing creators keep refusing what they refused; the frozen plans' workspaces are what they were.
+ *   avc_content_backward_ragged_params follows an avc_forward_ragged on the SAME plan, params, x and workspace; d_muls as for
+ * avc_content_backward_ragged.  It is that pass plus d(loss)/d(parameters) from the ragged weight-gradient kernel
+ * (csrc/conv_wgrad_ragged.hip): per block ONE launch with conv2's and conv1's jobs (the two heads ride in the first block's launch: their dy
+ * is the caller's d_muls), one launch with the in_conv and all bank members, then ONE reduce launch: n + 2 launches on top of the frozen
+ * pass (8 for the stock 6 blocks).  `grads` is the full flat gradient buffer: the pass OVERWRITES every tensor of the content encoder's range
+ * (avc_plan_param_range(AVC_GRADS_CONTENT); weights and biases -- the bias of a conv that feeds an InstanceNorm gets its mathematically zero
+ * gradient as the rounding residue of its row sums) and touches nothing else.
+ *   avc_decoder_backward_ragged_params follows an avc_decoder_forward_ragged on the SAME plan, params, z, zc, emb, seb, sec and workspace;
+ * here z and emb are READ (the in_conv's weight gradient reads the latent blocks in place, the 2 n AdaIN affine Linears' read emb through
+ * (seb, sec); seb = 0 is legal): they must be the forward's.  The jobs: out_conv (dy = the caller's d_dec) and the last block's two convs in
+ * one launch, one launch per other block, then the in_conv and the 2 n affine Linears (STRIDED jobs: dy = the layer's [N][2 c_h] slice of
+ * frame-major ws["d_cond"]) in one launch, then ONE reduce launch: n + 2 launches on top of the frozen pass.  The pass OVERWRITES every
+ * tensor of avc_plan_param_range(AVC_GRADS_DECODER) and touches nothing else; ws["d_z"] and ws["d_emb"] are the frozen pass's, bit for bit.
+ *   Both: no atomics, a fixed summation order (two passes give identical bits); every kernel goes to the caller's stream; the call only
+ * enqueues.  fp32 only (-8 when the plan's compute dtype is bf16); -8 with a message naming the creator on any other plan; -1 on a null
+ * argument. */
+int avc_plan_create_ragged_content_param_grads(const avc_model_cfg* cfg, int S, const int* T, const avc_tuning* tuning, avc_plan** out);
+int avc_content_backward_ragged_params(const avc_plan* p, const float* params, const float* x, const float* d_muls, float* grads, float* ws,
+                                       void* stream);
+int avc_plan_create_ragged_decoder_param_grads(const avc_model_cfg* cfg, int N, const int* Tz, const avc_tuning* tuning, avc_plan** out);
+int avc_decoder_backward_ragged_params(const avc_plan* p, const float* params, const float* z, int zc, const float* emb, long seb, long sec,
+                                       const float* d_dec, float* grads, float* ws, void* stream);
 
 /* L1 + KL losses of solver.py:84-86 -> ws["losses"] = {loss_rec, loss_kl}; writes
  * d(lambda_rec*loss_rec)/d(dec) into ws["d_dec"] for avc_backward. */
@@ -559,6 +589,17 @@ int avc_conv1d_wgrad(const float* x, long sxb, long sxc, int sxt, const float* d
 long avc_conv1d_wgrad_ragged_ws_floats(int B, const int* T, int Cin, int Cout, int KS, int stride);
 int avc_conv1d_wgrad_ragged(const float* x, int xC, int xc0, const float* dy, int dyC, int dyc0, int B, const int* T, int Cin, int Cout,
                             int KS, int stride, float* dW, float* db, float* ws, void* stream);
+/* ... of a Linear over N rows read through element strides: dW[co][ci] = sum_n dy(n, co) x(n, ci), db[co] = sum_n dy(n, co) with
+ * x(n, ci) = x[n sxn + ci sxc] and dy(n, co) = dy[n syn + co syc].  All strides >= 0 and spanning less than 2^31 elements; a row stride of 0
+ * is legal (every row reads the same one: an expanded single voice).  ONE strided job of the same kernel, the N rows are its frames: the
+ * staging loops run along whichever axis of each operand has stride 1 (coalesced loads either way), the chunks of 32 rows, the MFMA chain,
+ * the split-K slots and the slot-order reduce are avc_conv1d_wgrad_ragged's -- with sxn = syn = 1, sxc = syc = N the result is bit-identical
+ * to that call at B = 1, T = {N}, KS = 1.  dW [Cout][Cin] and db [Cout] (or NULL) are OVERWRITTEN.  ws: avc_linear_wgrad_strided_ws_floats
+ * floats (-1 for bad arguments).  No table, no copy from the host: the call only enqueues.  Two calls give identical bits.  -1 for a bad
+ * argument. */
+long avc_linear_wgrad_strided_ws_floats(int N, int Cin, int Cout);
+int avc_linear_wgrad_strided(const float* x, long sxn, long sxc, const float* dy, long syn, long syc, int N, int Cin, int Cout, float* dW,
+                             float* db, float* ws, void* stream);
 /* nn.InstanceNorm1d(affine=False) (model.py:296,341) [+ append_cond model.py:77-83] [+ ReLU] [+ residual:
  * 1 identity, 2 avg-pool(ceil), 5 nearest x2]; cond row b: beta = cond[b*cond_sb + cond_off + c], gamma = [.. + C + c] */
 /* relu: 0 = no activation, 1 = ReLU, 2 = LeakyReLU(0.01) */

@@ -61,7 +61,8 @@ def main():
                 torch.cuda.synchronize()
             r["sha256_" + what] = hashlib.sha256(ws.cpu().numpy().tobytes()).hexdigest()
 
-        if mode in ("decode", "decode_ig"):
+        grads = torch.zeros(plan.param_floats, device=dev) if mode in ("encode_pg", "decode_pg") else None
+        if mode in ("decode", "decode_ig", "decode_pg"):
             plan.forward_latents(params, z, plan.c_lat, emb, ws)
         elif mode in ("emb", "fanout"):
             plan.forward_emb(params, x, emb, ws)
@@ -74,9 +75,15 @@ def main():
             plan.backward_content(params, x, rnd(2 * plan.c_lat * sum(plan.lat_len), 7), ws)
         elif mode == "decode_ig":
             plan.backward_decoder(params, z, plan.c_lat, emb, rnd(M * sum(plan.out_len), 8), ws)
+        elif mode == "encode_pg":
+            plan.backward_content_params(params, x, rnd(2 * plan.c_lat * sum(plan.lat_len), 7), grads, ws)
+        elif mode == "decode_pg":
+            plan.backward_decoder_params(params, z, plan.c_lat, emb, rnd(M * sum(plan.out_len), 8), grads, ws)
         else:
             return r
         digest("backward")
+        if grads is not None:   # (the parameter-gradient kinds: the flat gradient buffer too)
+            r["sha256_grads"] = hashlib.sha256(grads.cpu().numpy().tobytes()).hexdigest()
         return r
 
     res = {}
@@ -97,6 +104,9 @@ def main():
             "decode": run(cfg, "decode", Tz, src_of=src_of),
             "decode_ig": run(cfg, "decode_ig", Tz),
         }
+        if hasattr(lib, "avc_plan_create_ragged_content_param_grads"):   # (absent from older builds: their nine kinds compare as they are)
+            res[name]["encode_pg"] = run(cfg, "encode_pg", T)
+            res[name]["decode_pg"] = run(cfg, "decode_pg", Tz)
     text = json.dumps(res, indent=1, sort_keys=True)
     if a.out:
         with open(a.out, "w") as f:
