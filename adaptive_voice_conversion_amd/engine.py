@@ -245,41 +245,58 @@ class Plan:
             n *= s
         return ws[off:off + n].view(*shape)
 
+    def num_sites(self):
+        return self.lib.avc_plan_num_relu_sites(self.h)
+
+    def site(self, ws, i):
+        """Site i of the plan's site table (avc_plan_relu_site; the reference's forward call order) decoded from the workspace as fp32
+        tensors (views where the storage is fp32): {"kind", "storage", "B", "C", "T"} plus
+        kind 0: "act" [B, C, T] -- the stored activation ([B, C] for the dense stack's channel-major [C][B] rows);
+        kind 1: "y" [B, C, T] -- the stored pre-norm conv output, "mean" / "rstd" [B, C, 1], "cond" [B, 2 C] (shift | scale) or None.
+        storage 0: fp32; 1: bf16 pair tensor; 2: natural ("planar") bf16 rows behind a pixel-shuffling conv."""
+        from ._lib import ReluSite
+        s = ReluSite()
+        if self.lib.avc_plan_relu_site(self.h, i, ctypes.byref(s)) != 0:
+            raise IndexError(i)
+        B, Cc, T = s.B, s.C, s.T
+        out = {"kind": s.kind, "storage": int(s.storage), "B": B, "C": Cc, "T": T}
+        wi = ws.view(torch.int32)
+        if s.kind == 0:
+            if s.storage == 1:
+                act = unpack_pairs(torch.as_strided(wi, (B, Cc // 2, T), (s.sb, s.sc, s.st), s.act_off))
+            else:
+                act = torch.as_strided(ws, (B, Cc, T), (s.sb, s.sc, s.st), s.act_off)
+            out["act"] = act.reshape(B, Cc) if (T == 1 and s.st == 0) else act
+            return out
+        if s.storage == 1:
+            y = unpack_pairs(wi[s.y_off:s.y_off + B * (Cc // 2) * T].view(B, Cc // 2, T))
+        elif s.storage == 2:
+            y = unpack_planar(wi[s.y_off:s.y_off + B * Cc * (T // 2)].view(B, Cc, T // 2))
+        else:
+            y = ws[s.y_off:s.y_off + B * Cc * T].view(B, Cc, T)
+        out["y"] = y
+        out["mean"] = ws[s.stat_off:s.stat_off + B * Cc].view(B, Cc, 1)
+        out["rstd"] = ws[s.stat_off + B * Cc:s.stat_off + 2 * B * Cc].view(B, Cc, 1)
+        out["cond"] = torch.as_strided(ws, (B, 2 * Cc), (s.cond_sb, 1), s.cond_off) if s.cond_off >= 0 else None
+        return out
+
     def relu_masks(self, ws):
         """0/1 masks of every ReLU of the last forward, in the reference's call order, computed
         from the engine's own saved tensors (diagnostics / branch-matched gradient checks)."""
-        import ctypes as C
-        from ._lib import ReluSite
         out = []
-        for i in range(self.lib.avc_plan_num_relu_sites(self.h)):
-            s = ReluSite()
-            self.lib.avc_plan_relu_site(self.h, i, C.byref(s))
-            B, Cc, T = s.B, s.C, s.T
-            if s.kind == 0:
-                if s.storage == 1:
-                    act = unpack_pairs(torch.as_strided(ws.view(torch.int32), (B, Cc // 2, T), (s.sb, s.sc, s.st), s.act_off))
-                else:
-                    act = torch.as_strided(ws, (B, Cc, T), (s.sb, s.sc, s.st), s.act_off)
-                m = act > 0
-                if T == 1 and s.st == 0:
-                    m = m.reshape(B, Cc)
+        for i in range(self.num_sites()):
+            s = self.site(ws, i)
+            if s["kind"] == 0:
+                out.append(s["act"] > 0)
+                continue
+            Cc = s["C"]
+            xh = ((s["y"] - s["mean"]) * s["rstd"]).double()      # the same two fp32 roundings as the kernel
+            if s["cond"] is not None:
+                cond = s["cond"].double()
+                w = xh * cond[:, Cc:, None] + cond[:, :Cc, None]   # exact in fp64 -> same sign as the fp32 fma
             else:
-                if s.storage == 1:
-                    y = unpack_pairs(ws.view(torch.int32)[s.y_off:s.y_off + B * (Cc // 2) * T].view(B, Cc // 2, T))
-                elif s.storage == 2:
-                    y = unpack_planar(ws.view(torch.int32)[s.y_off:s.y_off + B * Cc * (T // 2)].view(B, Cc, T // 2))
-                else:
-                    y = ws[s.y_off:s.y_off + B * Cc * T].view(B, Cc, T)
-                mean = ws[s.stat_off:s.stat_off + B * Cc].view(B, Cc, 1)
-                rstd = ws[s.stat_off + B * Cc:s.stat_off + 2 * B * Cc].view(B, Cc, 1)
-                xh = ((y - mean) * rstd).double()      # the same two fp32 roundings as the kernel
-                if s.cond_off >= 0:
-                    cond = torch.as_strided(ws, (B, 2 * Cc), (s.cond_sb, 1), s.cond_off).double()
-                    w = xh * cond[:, Cc:, None] + cond[:, :Cc, None]   # exact in fp64 -> same sign as the fp32 fma
-                else:
-                    w = xh
-                m = w > 0
-            out.append(m)
+                w = xh
+            out.append(w > 0)
         return out
 
     def _chk(self, rc):
