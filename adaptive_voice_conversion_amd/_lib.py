@@ -124,6 +124,13 @@ def declare(lib):
         lib.avc_linear_wgrad_strided_ws_floats.restype = c_long
         lib.avc_linear_wgrad_strided.argtypes = [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                                  c_void_p]
+    if hasattr(lib, "avc_loss_ragged"):   # (likewise)
+        lib.avc_reparam_ragged.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
+        lib.avc_loss_ragged_ws_floats.argtypes = [c_int, c_int]
+        lib.avc_loss_ragged_ws_floats.restype = c_long
+        lib.avc_loss_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_int, c_long, c_long, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.avc_latent_bwd_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]
     lib.avc_gather_segments.argtypes =[c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.avc_plan_destroy.argtypes = [c_void_p]
     lib.avc_plan_destroy.restype = None

@@ -677,3 +677,87 @@ class RaggedPlan:
     def outputs(self, ws):
         """list of [M, out_len[b]] views of the converted utterances in the workspace"""
         return _blocks(ws, self.out_off[0], self.n_mels, self.out_len) if self.out_len else []
+
+
+class RaggedLossTables:
+    """The device tables the loss-side calls of a ragged training step read (avc_reparam_ragged, avc_loss_ragged, avc_latent_bwd_ragged),
+    built ONCE per tuple of lengths and kept with the plans: ``T`` frames of every utterance, ``out_len`` / ``out_off`` of the decoder plan
+    (avc_plan_ragged_out; the offsets are stored relative to the first block), ``Tz`` latent frames.  int32 (out_off: int64) on ``device``;
+    building them is the only host-to-device copy of the loss side."""
+
+    def __init__(self, T, out_len, out_off, Tz, device):
+        self.T, self.out_len, self.Tz = [int(t) for t in T], [int(t) for t in out_len], [int(t) for t in Tz]
+        self.N = len(self.T)
+        if not self.N or len(self.out_len) != self.N or len(self.Tz) != self.N or len(out_off) != self.N:
+            raise ValueError("T, out_len, out_off and Tz must be equally long, non-empty lists")
+        if any(t < 1 for t in self.T + self.Tz) or any(o < t for o, t in zip(self.out_len, self.T)):
+            raise ValueError("every length must be at least 1 and every output block at least as long as its utterance")
+        self.out_off = [int(o) - int(out_off[0]) for o in out_off]
+        prefix = lambda v: [sum(v[:i]) for i in range(len(v))]
+        self.sum_T, self.sum_out, self.sum_Tz = sum(self.T), sum(self.out_len), sum(self.Tz)
+        self.T_max, self.Tz_max = max(self.out_len), max(self.Tz)
+        ints = torch.tensor(self.T + prefix(self.T) + self.out_len + self.Tz + prefix(self.Tz), dtype=torch.int32).to(device)
+        N = self.N
+        self.T_dev, self.xoff_dev, self.out_len_dev, self.Tz_dev, self.offz_dev = (ints[i * N:(i + 1) * N] for i in range(5))
+        self.out_off_dev = torch.tensor(self.out_off, dtype=torch.int64).to(device)
+        self.device = ints.device
+
+    def dec_floats(self, M):
+        """floats from the first output block to the end of the last"""
+        return self.out_off[-1] + M * self.out_len[-1]
+
+
+def _rl_check(rc, what):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed: {rc}")
+
+
+def reparam_ragged(lib, muls, eps, tab, c, z):
+    """z = mu + exp(log_sigma / 2) * eps on packed latent blocks (avc_reparam_ragged): muls = the ws["muls"] region of a ragged plan with a
+    content encoder (block s = [2 c][Tz_s]), eps / z blocks [c][Tz_s]; eps None: z = mu.  Overwrites z; only enqueues."""
+    n = c * tab.sum_Tz
+    _packed(muls, 2 * n, "muls", " (mu | log_sigma blocks)", muls, at_least=True)
+    _packed(z, n, "z", "", muls, at_least=True)
+    if eps is not None:
+        _packed(eps, n, "eps", " (one value per latent element)", muls)
+    with _on(muls):
+        _rl_check(lib.avc_reparam_ragged(_ptr(muls), _ptr(eps), tab.N, _ptr(tab.Tz_dev), _ptr(tab.offz_dev), tab.Tz_max, c, _ptr(z), _stream(muls)),
+                  "avc_reparam_ragged")
+
+
+def loss_ragged_ws_floats(lib, tab):
+    n = lib.avc_loss_ragged_ws_floats(tab.N, tab.T_max)
+    if n < 0:
+        raise RuntimeError("avc_loss_ragged_ws_floats: bad counts")
+    return n
+
+
+def loss_ragged(lib, dec, x, muls, tab, M, c, lambda_rec, d_dec, losses, ws):
+    """L1 + KL loss of a ragged step and d(lambda_rec * loss_rec)/d(dec) (avc_loss_ragged): dec = the output region of the decoder plan
+    (block j = [M][out_len_j]), x = the packed [sum T, M] rows, muls as in ``reparam_ragged``.  Overwrites d_dec (every element of every
+    block: the crop tail gets zeros), losses[0:2] = (loss_rec, loss_kl) and ws (``loss_ragged_ws_floats``); only enqueues."""
+    nd = tab.dec_floats(M)
+    _packed(dec, nd, "dec", " (the layout of the decoder plan's output blocks)", dec, at_least=True)
+    _packed(d_dec, nd, "d_dec", " (the layout of the decoder plan's output blocks)", dec, at_least=True)
+    _packed(x, tab.sum_T * M, "x", " (the packed rows)", dec)
+    _packed(muls, 2 * c * tab.sum_Tz, "muls", " (mu | log_sigma blocks)", dec, at_least=True)
+    _packed(losses, 2, "losses", "", dec, at_least=True)
+    _packed(ws, loss_ragged_ws_floats(lib, tab), "ws", "", dec, at_least=True)
+    with _on(dec):
+        _rl_check(lib.avc_loss_ragged(_ptr(dec), _ptr(tab.out_len_dev), _ptr(tab.out_off_dev), _ptr(x), _ptr(tab.T_dev), _ptr(tab.xoff_dev), tab.N, M,
+                                      tab.T_max, _ptr(muls), _ptr(tab.Tz_dev), _ptr(tab.offz_dev), c, tab.sum_T * M, tab.sum_Tz * c,
+                                      float(lambda_rec), _ptr(d_dec), _ptr(losses), _ptr(ws), _stream(dec)), "avc_loss_ragged")
+
+
+def latent_bwd_ragged(lib, muls, eps, d_z, tab, c, lambda_kl_over_n, d_muls):
+    """d(loss)/d(mu | log_sigma) from the KL term and from d_z (avc_latent_bwd_ragged); eps None: the z = mu step.  Overwrites d_muls (the
+    layout of muls); only enqueues."""
+    n = c * tab.sum_Tz
+    _packed(muls, 2 * n, "muls", " (mu | log_sigma blocks)", muls, at_least=True)
+    _packed(d_z, n, "d_z", "", muls, at_least=True)
+    _packed(d_muls, 2 * n, "d_muls", " (the layout of muls)", muls, at_least=True)
+    if eps is not None:
+        _packed(eps, n, "eps", " (one value per latent element)", muls)
+    with _on(muls):
+        _rl_check(lib.avc_latent_bwd_ragged(_ptr(muls), _ptr(eps), _ptr(d_z), tab.N, _ptr(tab.Tz_dev), _ptr(tab.offz_dev), tab.Tz_max, c,
+                                            float(lambda_kl_over_n), _ptr(d_muls), _stream(muls)), "avc_latent_bwd_ragged")

@@ -122,11 +122,14 @@ class Solver(object):
         self._ar_events = []
 
     # ---- one training step (solver.py:81-97) -------------------------------------
-    def _draw_eps(self, B, C, Tb, device):
+    def _eps_generator(self, device):
         if self._eps_gen is None or self._eps_gen.device != device:
             self._eps_gen = torch.Generator(device=device)
             self._eps_gen.manual_seed(torch.initial_seed() + 7919 * self._rank())
-        return torch.randn(B, C, Tb, device=device, dtype=torch.float32, generator=self._eps_gen)
+        return self._eps_gen
+
+    def _draw_eps(self, B, C, Tb, device):
+        return torch.randn(B, C, Tb, device=device, dtype=torch.float32, generator=self._eps_generator(device))
 
     def _allreduce_grads(self, d, plan, grads):
         """SUM over ranks of the flat gradient buffer (RCCL over xGMI when the backend is "nccl"); the 1/W of the
@@ -254,6 +257,112 @@ class Solver(object):
         if not sync:
             return {"loss_rec": losses[0], "loss_kl": losses[1], "grad_norm": gnorm[0]}
         vals = torch.cat([losses, gnorm]).tolist()  # one D2H sync (the reference does .item() x2, solver.py:94-95)
+        return {"loss_rec": vals[0], "loss_kl": vals[1], "grad_norm": vals[2]}
+
+    # ---- one training step over whole utterances of different lengths ----------------
+    def _rag_buf(self, name, n, device):
+        """the first n floats of a buffer this Solver owns; it grows on demand and is reused from step to step"""
+        bufs = self.__dict__.setdefault("_rag_bufs", {})
+        b = bufs.get(name)
+        if b is None or b.device != device or b.numel() < n:
+            b = bufs[name] = torch.empty(int(n * 1.25) + 64, dtype=torch.float32, device=device)
+        return b[:n]
+
+    def _rag_state(self, T):
+        """(three grad plans with the workspaces this step runs in, RaggedLossTables) of a tuple of lengths.  The plans are the AE's
+        ("encode_pg", "speaker_pg", "decode_pg" of AE._ragged_plan: the ones the ragged autograd functions use); a workspace that still holds
+        the activations of a pending autograd backward is left alone and the step runs in a private one, as _PartFunction._attach does."""
+        from .engine import RaggedLossTables
+        model = self.model
+        dev = model.flat_parameters().device
+        pe, ee = model._ragged_plan("encode_pg", T, ())
+        ps, es = model._ragged_plan("speaker_pg", (), T)
+        Tz = tuple(pe.lat_len)
+        pd, ed = model._ragged_plan("decode_pg", Tz, ())
+        wss = [e.ws if not e.busy() else torch.zeros(p.workspace_floats, dtype=torch.float32, device=dev) for p, e in ((pe, ee), (ps, es), (pd, ed))]
+        tabs = self.__dict__.setdefault("_rag_tables", {})
+        key = (T, str(dev))
+        tab = tabs.pop(key, None)
+        if tab is None:
+            tab = RaggedLossTables(T, pd.out_len, pd.out_off, Tz, dev)
+        tabs[key] = tab   # most recently used last
+        while len(tabs) > 4:
+            tabs.pop(next(iter(tabs)))
+        return (pe, ps, pd), wss, tab
+
+    def ae_step_ragged(self, utts, lambda_kl, eps=None, sync=True, apply=True):
+        """``ae_step`` over whole utterances of DIFFERENT lengths: ``utts`` is a list of [T_j, M] tensors (frames as rows, what
+        ``AE.inference_ragged`` takes); every utterance is both content source and speaker reference, as ``model(x)`` in the reference's
+        ae_step (solver.py:83, model.py:376-385).  The loss is the reference's on the packed rows: mean |dec[:, :T_j] - x_j| over all kept
+        elements, 0.5 mean(exp(ls) + mu^2 - 1 - ls) over all latent elements, z = mu + exp(ls / 2) * eps.
+
+        One pass through the three ragged grad plans ("encode_pg", "speaker_pg", "decode_pg") with the packed-row loss kernels between them
+        (avc_reparam_ragged, avc_loss_ragged, avc_latent_bwd_ragged).  The three backward passes write their networks' ranges of
+        ``model.flat_grads()`` directly -- together the whole buffer -- and the fused clip+Adam kernel reads it from there: no temporary
+        gradient buffer, no ``.grad`` accumulation, no copy of a workspace region.  z, eps, d_dec, d_muls, the loss workspace and the
+        length tables belong to this Solver, grow on demand and are reused.
+
+        eps: None draws c_lat * sum(Tz) values from this rank's own generator (as ``ae_step``); a tensor of that many fp32 elements (block j
+        = [c_lat][Tz_j], back to back) is used as given; False: no noise (z = mu).  apply=False stops before the optimizer: parameters and
+        optimizer state stay untouched, the gradients stay in ``model.flat_grads()`` and no "grad_norm" is returned.  sync=False returns
+        device scalars without waiting.  fp32 only, one process only: ``compute_dtype`` bf16 and a world size above 1 are refused (the
+        per-rank means over packed rows do not average to the global mean)."""
+        from .engine import latent_bwd_ragged, loss_ragged, loss_ragged_ws_floats, reparam_ragged
+        model = self.model
+        if str(model.compute_dtype).lower().startswith(("bf16", "bfloat16")):
+            raise RuntimeError(f"ae_step_ragged: the ragged gradient passes are fp32 only, and compute_dtype is {model.compute_dtype!r}; "
+                               "train on equal-length segments with ae_step")
+        d = _dist()
+        if d is not None and d.get_world_size() > 1:
+            raise RuntimeError(f"ae_step_ragged: one process only (world size {d.get_world_size()}): the means over each rank's packed rows "
+                               "do not average to the mean over all ranks' rows; train on equal-length segments with ae_step")
+        utts = list(utts)
+        if not utts:
+            raise ValueError("ae_step_ragged: an empty list of utterances")
+        T, x = model._ragged_rows(utts, "utts")
+        flat, grads = model.flat_parameters(), model.flat_grads()
+        dev = flat.device
+        (pe, ps, pd), (wse, wss, wsd), tab = self._rag_state(T)
+        lib, c, M = pe.lib, pe.c_lat, pe.n_mels
+        n_lat = c * tab.sum_Tz
+        if eps is None:
+            eps = self._rag_buf("eps", n_lat, dev).normal_(generator=self._eps_generator(dev))   # model.py:383
+        elif eps is False:
+            eps = None
+        else:
+            if not torch.is_tensor(eps) or eps.numel() != n_lat or eps.dtype != torch.float32:
+                raise ValueError(f"ae_step_ragged: eps must be an fp32 tensor of {n_lat} elements (block j = [{c}][Tz_j], Tz = {tab.Tz}), "
+                                 "None (draw it) or False (no noise)")
+            eps = eps.to(dev).contiguous().view(-1)
+        pe.forward(flat, x, None, wse)
+        ps.forward(flat, None, x, wss)
+        muls = wse[pe.lat_off[0]:pe.lat_off[0] + 2 * n_lat]
+        z = self._rag_buf("z", n_lat, dev)
+        reparam_ragged(lib, muls, eps, tab, c, z)
+        emb = ps.emb(wss)   # read in place from the speaker plan's workspace
+        pd.forward_latents(flat, z, c, emb, wsd)
+        n_dec = M * tab.sum_out
+        dec = wsd[pd.out_off[0]:pd.out_off[0] + n_dec]
+        d_dec, losses = self._rag_buf("d_dec", n_dec, dev), self._rag_buf("losses", 2, dev)
+        loss_ragged(lib, dec, x, muls, tab, M, c, self.config["lambda"]["lambda_rec"], d_dec, losses,
+                    self._rag_buf("loss_ws", loss_ragged_ws_floats(lib, tab), dev))
+        pd.backward_decoder_params(flat, z, c, emb, d_dec, grads, wsd)
+        o = pd.buffer("d_z")
+        d_muls = self._rag_buf("d_muls", 2 * n_lat, dev)
+        latent_bwd_ragged(lib, muls, eps, wsd[o:o + n_lat], tab, c, float(lambda_kl) / n_lat, d_muls)
+        pe.backward_content_params(flat, x, d_muls, grads, wse)
+        ps.backward_params(flat, x, pd.d_emb(wsd), grads, wss)
+        self._rag_last = ((pe, ps, pd), (wse, wss, wsd), tab)   # (the workspaces of the last step: saved rows, dec)
+        if not apply:
+            if not sync:
+                return {"loss_rec": losses[0], "loss_kl": losses[1]}
+            vals = losses.tolist()   # one D2H sync
+            return {"loss_rec": vals[0], "loss_kl": vals[1]}
+        gnorm = self.opt.step(self.config["optimizer"]["grad_norm"])
+        model.weights_changed()   # (the kernel writes the flat buffer behind torch's version counters: ae_step's packed weight images are stale)
+        if not sync:
+            return {"loss_rec": losses[0], "loss_kl": losses[1], "grad_norm": gnorm[0]}
+        vals = torch.cat([losses, gnorm]).tolist()  # one D2H sync
         return {"loss_rec": vals[0], "loss_kl": vals[1], "grad_norm": vals[2]}
 
     @staticmethod

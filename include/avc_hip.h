@@ -626,6 +626,36 @@ int avc_conv1d_dgrad_in_bwd(const float* dy, long syb, long syc, int syt, int yp
                             const float* rstd, const float* cond, long cond_sb, int cond_off, int relu, float* dy_out, float* dcond,
                             long dcond_sb, int dcond_off, int* fused, void* stream);
 
+/* ---- loss side of a training step over utterances of DIFFERENT lengths (csrc/ragged_loss.hip) ----
+ * Shared by the four calls below.  Latent blocks: sample s of muls / d_muls is a [2 c][Tz[s]] block (frames contiguous; the c mu rows, then
+ * the c log_sigma rows) at float offset 2 c offz[s]; sample s of z / eps / d_z is a [c][Tz[s]] block at c offz[s] -- the layouts of the ragged
+ * plans' ws["muls"] and ws["d_z"] regions.  Tz_dev / offz_dev are DEVICE int32 tables of S entries the caller built (offz = prefix sums of
+ * Tz, every Tz[s] >= 1); Tz_max >= every Tz[s] sizes the grid.  fp32 only.  Each call ONLY ENQUEUES on `stream`: no allocation, no copy from
+ * the host, no synchronisation -- graph-capture safe.  No atomics, a fixed summation order: two calls give identical bits.  0 on success,
+ * -1 for a null argument (eps alone may be NULL) or a bad count (S, N outside 1..65535; a length bound, c, M, n_rec or n_kl below 1). */
+/* z = mu + exp(log_sigma / 2) * eps (model.py:383-384; the uniform engine's expression); eps NULL: z = mu.  OVERWRITES the c sum(Tz) floats of
+ * z, nothing else. */
+int avc_reparam_ragged(const float* muls, const float* eps, int S, const int* Tz_dev, const int* offz_dev, int Tz_max, int c, float* z,
+                       void* stream);
+/* L1 + KL loss (solver.py:84-86) on packed rows, and d(loss_rec * lambda_rec)/d(dec).  x: utterance j is rows [T[j]][M] (mel bins contiguous)
+ * at row xoff[j] (xoff = prefix sums of T); dec / d_dec: block j is [M][out_len[j]] (frames contiguous) at float offset out_off[j] from the
+ * pointer passed (avc_plan_ragged_out's offsets minus the first), out_len[j] >= T[j] >= 1: frames t < T[j] count, the crop tail
+ * T[j] <= t < out_len[j] is ignored.  T_dev / xoff_dev / out_len_dev (int32) and out_off_dev (int64) are DEVICE tables of N entries;
+ * T_max >= every out_len[j].  Latent block j (above; S = N) feeds the KL term.  n_rec = M sum(T), n_kl = c sum(Tz).
+ * OVERWRITES every element of every d_dec block exactly once: lambda_rec / n_rec (divided in double, rounded once) times sign(dec - x) for
+ * t < T[j], 0 in the crop tail; losses[0] = mean |dec - x| over the n_rec kept elements, losses[1] = 0.5 mean(exp(ls) + mu^2 - 1 - ls)
+ * over the n_kl latent elements; and the avc_loss_ragged_ws_floats(N, T_max) floats of ws (partial sums; -1 for a bad count). */
+long avc_loss_ragged_ws_floats(int N, int T_max);
+int avc_loss_ragged(const float* dec, const int* out_len_dev, const long* out_off_dev, const float* x, const int* T_dev, const int* xoff_dev, int N,
+                    int M, int T_max, const float* muls, const int* Tz_dev, const int* offz_dev, int c, long n_rec, long n_kl, float lambda_rec,
+                    float* d_dec, float* losses, float* ws, void* stream);
+/* d(loss)/d(mu | log_sigma) from the KL term and from d_z = d(loss)/d(z): d_mu = lambda_kl_over_n mu + d_z, d_ls = lambda_kl_over_n 0.5
+ * (exp(ls) - 1) + d_z eps 0.5 exp(ls / 2) (the uniform engine's expressions; lambda_kl_over_n = lambda_kl / n_kl); eps NULL (z = mu): no
+ * second term of d_ls.  Products and sums are rounded one by one (no fused multiply-add).  OVERWRITES the 2 c sum(Tz) floats of d_muls,
+ * nothing else. */
+int avc_latent_bwd_ragged(const float* muls, const float* eps, const float* d_z, int S, const int* Tz_dev, const int* offz_dev, int Tz_max, int c,
+                          float lambda_kl_over_n, float* d_muls, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
