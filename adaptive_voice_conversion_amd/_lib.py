@@ -131,6 +131,8 @@ def declare(lib):
         lib.avc_loss_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         c_int, c_long, c_long, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.avc_latent_bwd_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]
+    if hasattr(lib, "avc_gather_utterances"):   # (likewise)
+        lib.avc_gather_utterances.argtypes = [c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.avc_gather_segments.argtypes =[c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.avc_plan_destroy.argtypes = [c_void_p]
     lib.avc_plan_destroy.restype = None

@@ -732,10 +732,12 @@ def loss_ragged_ws_floats(lib, tab):
     return n
 
 
-def loss_ragged(lib, dec, x, muls, tab, M, c, lambda_rec, d_dec, losses, ws):
+def loss_ragged(lib, dec, x, muls, tab, M, c, lambda_rec, d_dec, losses, ws, n_rec=None, n_kl=None):
     """L1 + KL loss of a ragged step and d(lambda_rec * loss_rec)/d(dec) (avc_loss_ragged): dec = the output region of the decoder plan
     (block j = [M][out_len_j]), x = the packed [sum T, M] rows, muls as in ``reparam_ragged``.  Overwrites d_dec (every element of every
-    block: the crop tail gets zeros), losses[0:2] = (loss_rec, loss_kl) and ws (``loss_ragged_ws_floats``); only enqueues."""
+    block: the crop tail gets zeros), losses[0:2] = (loss_rec, loss_kl) and ws (``loss_ragged_ws_floats``); only enqueues.
+    n_rec / n_kl: the normalisers of the two means, default the counts of THESE rows (M sum T, c sum Tz); a data-parallel rank passes the
+    counts of all ranks' rows and gets its share of the global means, which then add up over the ranks."""
     nd = tab.dec_floats(M)
     _packed(dec, nd, "dec", " (the layout of the decoder plan's output blocks)", dec, at_least=True)
     _packed(d_dec, nd, "d_dec", " (the layout of the decoder plan's output blocks)", dec, at_least=True)
@@ -745,7 +747,8 @@ def loss_ragged(lib, dec, x, muls, tab, M, c, lambda_rec, d_dec, losses, ws):
     _packed(ws, loss_ragged_ws_floats(lib, tab), "ws", "", dec, at_least=True)
     with _on(dec):
         _rl_check(lib.avc_loss_ragged(_ptr(dec), _ptr(tab.out_len_dev), _ptr(tab.out_off_dev), _ptr(x), _ptr(tab.T_dev), _ptr(tab.xoff_dev), tab.N, M,
-                                      tab.T_max, _ptr(muls), _ptr(tab.Tz_dev), _ptr(tab.offz_dev), c, tab.sum_T * M, tab.sum_Tz * c,
+                                      tab.T_max, _ptr(muls), _ptr(tab.Tz_dev), _ptr(tab.offz_dev), c, int(tab.sum_T * M if n_rec is None else n_rec),
+                                      int(tab.sum_Tz * c if n_kl is None else n_kl),
                                       float(lambda_rec), _ptr(d_dec), _ptr(losses), _ptr(ws), _stream(dec)), "avc_loss_ragged")
 
 

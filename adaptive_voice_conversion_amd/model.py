@@ -574,6 +574,9 @@ class AE(nn.Module):
         # "encode" | "decode" | "speaker_ig" (the
         # speaker plan with input gradients; the key carries the flag, and only it has an _Entry: a workspace of its own)
         self._ragged = {}
+        # how many of them (`ragged_plan_cache` in the config; set_ragged_plan_cache): a training loop over K length templates needs
+        # 3 K grad plans to stay (Solver.train_ragged raises the bound), everything else lives with a few
+        self._ragged_cap = max(1, int((config.get("ragged_plan_cache") if isinstance(config, dict) else None) or 4))
         self._ragged_ws = None   # the one workspace the forward-only plans share
         self.last_ragged_compute = None
 
@@ -657,6 +660,11 @@ class AE(nn.Module):
             if v is not None:
                 self._plans.capacity[k] = max(1, int(v))
 
+    def set_ragged_plan_cache(self, n):
+        """How many ragged plans of all modes (with the workspaces the grad plans own) are kept, most recently used last (the config's
+        ``ragged_plan_cache``, default 4).  Takes effect when the next plan is created; a smaller bound evicts then."""
+        self._ragged_cap = max(1, int(n))
+
     def _outputs(self, plan, ws):
         B = plan.B
         muls = plan.view(ws, "muls", (B, 2 * self._c_lat, plan.latent_len))
@@ -725,7 +733,7 @@ class AE(nn.Module):
             if [(o, n) for o, n, _ in plan.param_info] != [(o, n) for o, n, _ in self._layout]:
                 raise RuntimeError("flat parameter layout of the C plan differs from the module's")
             hit = self._ragged[key] = (plan, _Entry(plan, torch.zeros(plan.workspace_floats, dtype=torch.float32, device=dev)) if ig else None)
-            while len(self._ragged) > 4:
+            while len(self._ragged) > self._ragged_cap:
                 old = self._ragged.pop(next(iter(self._ragged)))
                 if old[1] is None:   # (a grad plan may still be needed by a pending backward -- also one that ran in a private workspace, which
                     old[0].close()   # the entry does not track: it is never closed here, RaggedPlan.__del__ releases it once no graph holds it)

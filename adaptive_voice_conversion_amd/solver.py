@@ -81,6 +81,19 @@ class Solver(object):
     # ---- data (solver.py:57-68) ----------------------------------------------
     def get_data_loaders(self):
         d = self.args.data_dir
+        if getattr(self.args, "ragged_feed", False):
+            from .device_feed import RaggedUtteranceFeed
+            rank, world = 0, 1
+            dd = _dist()
+            if dd is not None:
+                rank, world = dd.get_rank(), dd.get_world_size()
+            dev = local_device() if self._lib is None else torch.device("cpu")   # (an injected library: the CPU simulation of the tests)
+            self.ragged_iter = RaggedUtteranceFeed.from_files(
+                os.path.join(d, f"{self.args.train_set}.pkl"), self.config["data_loader"]["batch_size"], dev,
+                n_templates=getattr(self.args, "ragged_templates", 8), min_frames=getattr(self.args, "ragged_min_frames", 17),
+                max_frames=getattr(self.args, "ragged_max_frames", None), seed=0, rank=rank, world_size=world,   # ONE stream of draws, shared
+                lib=self._lib)
+            return
         if getattr(self.args, "device_feed", False):
             from .device_feed import DeviceSegmentFeed
             rank, world = 0, 1
@@ -286,9 +299,48 @@ class Solver(object):
         if tab is None:
             tab = RaggedLossTables(T, pd.out_len, pd.out_off, Tz, dev)
         tabs[key] = tab   # most recently used last
-        while len(tabs) > 4:
+        while len(tabs) > getattr(self, "_rag_tables_cap", 4):
             tabs.pop(next(iter(tabs)))
         return (pe, ps, pd), wss, tab
+
+    def _latent_frames(self, T):
+        """latent frames of an utterance of T frames: the content encoder halves (rounding up) at every block that subsamples -- the
+        ``lat_len`` of a content plan, computed on the host for lengths this rank holds no plan of (the other ranks' utterances)"""
+        ce = self.config["ContentEncoder"]
+        for s in ce["subsample"][:ce["n_conv_blocks"]]:
+            if s > 1:
+                T = -(-T // s)
+        return T
+
+    def _packed_rows(self, batch):
+        """the checks ``AE._ragged_rows`` makes, on a batch that is packed already: (T, x) with x used in place"""
+        model = self.model
+        x, T = batch.x, batch.T
+        M, dev = model._n_mels, model.flat_parameters().device
+        if not T or any(t < 1 for t in T) or any(t < 1 for t in batch.global_T):
+            raise ValueError("ae_step_ragged: a PackedUtterances needs at least one utterance and lengths of at least 1")
+        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] != M or x.shape[0] != sum(T):
+            raise ValueError(f"ae_step_ragged: PackedUtterances.x must be the packed [sum T, {M}] = [{sum(T)}, {M}] rows (frames as rows), got "
+                             f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError(f"ae_step_ragged: PackedUtterances.x must be contiguous fp32, got {x.dtype}, strides {tuple(x.stride())}")
+        if x.device != dev:
+            raise RuntimeError(f"ae_step_ragged: PackedUtterances.x on {x.device} but parameters on {dev}")
+        return T, x
+
+    def _allreduce_ragged(self, d, grads, losses):
+        """SUM over ranks of the flat gradient buffer, ONE bucket behind the whole backward (every rank divided by the global counts, so the
+        sum IS the global-mean gradient: no 1/W anywhere), in the wire format of ``allreduce_dtype``; then of the two loss floats (always
+        fp32: they are reported, not stepped on)."""
+        if self.config.get("allreduce_dtype", "fp32") == "bf16":
+            if self._wire is None or self._wire.device != grads.device or self._wire.numel() != grads.numel():
+                self._wire = torch.empty(grads.numel(), dtype=torch.bfloat16, device=grads.device)
+            self._wire.copy_(grads)
+            d.all_reduce(self._wire)
+            grads.copy_(self._wire)
+        else:
+            d.all_reduce(grads)
+        d.all_reduce(losses)
 
     def ae_step_ragged(self, utts, lambda_kl, eps=None, sync=True, apply=True):
         """``ae_step`` over whole utterances of DIFFERENT lengths: ``utts`` is a list of [T_j, M] tensors (frames as rows, what
@@ -305,26 +357,44 @@ class Solver(object):
         eps: None draws c_lat * sum(Tz) values from this rank's own generator (as ``ae_step``); a tensor of that many fp32 elements (block j
         = [c_lat][Tz_j], back to back) is used as given; False: no noise (z = mu).  apply=False stops before the optimizer: parameters and
         optimizer state stay untouched, the gradients stay in ``model.flat_grads()`` and no "grad_norm" is returned.  sync=False returns
-        device scalars without waiting.  fp32 only, one process only: ``compute_dtype`` bf16 and a world size above 1 are refused (the
-        per-rank means over packed rows do not average to the global mean)."""
+        device scalars without waiting.  fp32 only (``compute_dtype`` bf16 is refused); a list is for one process only: a world size above
+        1 is refused (the per-rank means over packed rows do not average to the global mean).
+
+        ``utts`` may also be the ``PackedUtterances`` of a ``RaggedUtteranceFeed``: its ``x`` is used in place (no ``torch.cat``), and the
+        two means are taken over ``global_T``, the lengths of ALL ranks' utterances: n_rec = M sum(global_T) and n_kl = c sum(Tz) go to the
+        loss kernels in place of this rank's counts, so every rank computes its exact share of the global-mean gradient.  Any world size
+        is accepted: the flat gradient buffer is summed over the ranks behind the three backward passes (one bucket, the wire format of
+        ``allreduce_dtype``, no 1/W in the optimizer), and so are the two losses -- every rank returns the global means.  With one
+        process and global_T == T the gradients are bit-equal to the list call's on the same rows."""
         from .engine import latent_bwd_ragged, loss_ragged, loss_ragged_ws_floats, reparam_ragged
         model = self.model
         if str(model.compute_dtype).lower().startswith(("bf16", "bfloat16")):
             raise RuntimeError(f"ae_step_ragged: the ragged gradient passes are fp32 only, and compute_dtype is {model.compute_dtype!r}; "
                                "train on equal-length segments with ae_step")
+        from .device_feed import PackedUtterances
         d = _dist()
-        if d is not None and d.get_world_size() > 1:
-            raise RuntimeError(f"ae_step_ragged: one process only (world size {d.get_world_size()}): the means over each rank's packed rows "
-                               "do not average to the mean over all ranks' rows; train on equal-length segments with ae_step")
-        utts = list(utts)
-        if not utts:
-            raise ValueError("ae_step_ragged: an empty list of utterances")
-        T, x = model._ragged_rows(utts, "utts")
+        packed = isinstance(utts, PackedUtterances)
+        if packed:
+            T, x = self._packed_rows(utts)
+        else:
+            if d is not None and d.get_world_size() > 1:
+                raise RuntimeError(f"ae_step_ragged: one process only (world size {d.get_world_size()}) for a list of utterances: the means over "
+                                   "each rank's packed rows do not average to the mean over all ranks' rows; pass the PackedUtterances of a "
+                                   "RaggedUtteranceFeed (they carry all ranks' lengths), or train on equal-length segments with ae_step")
+            utts = list(utts)
+            if not utts:
+                raise ValueError("ae_step_ragged: an empty list of utterances")
+            T, x = model._ragged_rows(utts, "utts")
         flat, grads = model.flat_parameters(), model.flat_grads()
         dev = flat.device
         (pe, ps, pd), (wse, wss, wsd), tab = self._rag_state(T)
         lib, c, M = pe.lib, pe.c_lat, pe.n_mels
         n_lat = c * tab.sum_Tz
+        n_rec, n_kl = M * tab.sum_T, n_lat   # the normalisers of the two means: the counts of all ranks' rows
+        if packed:
+            if [self._latent_frames(t) for t in T] != list(tab.Tz):
+                raise RuntimeError("ae_step_ragged: the host rule for latent lengths disagrees with the content plan's")
+            n_rec, n_kl = M * sum(utts.global_T), c * sum(self._latent_frames(t) for t in utts.global_T)
         if eps is None:
             eps = self._rag_buf("eps", n_lat, dev).normal_(generator=self._eps_generator(dev))   # model.py:383
         elif eps is False:
@@ -345,14 +415,16 @@ class Solver(object):
         dec = wsd[pd.out_off[0]:pd.out_off[0] + n_dec]
         d_dec, losses = self._rag_buf("d_dec", n_dec, dev), self._rag_buf("losses", 2, dev)
         loss_ragged(lib, dec, x, muls, tab, M, c, self.config["lambda"]["lambda_rec"], d_dec, losses,
-                    self._rag_buf("loss_ws", loss_ragged_ws_floats(lib, tab), dev))
+                    self._rag_buf("loss_ws", loss_ragged_ws_floats(lib, tab), dev), n_rec=n_rec, n_kl=n_kl)
         pd.backward_decoder_params(flat, z, c, emb, d_dec, grads, wsd)
         o = pd.buffer("d_z")
         d_muls = self._rag_buf("d_muls", 2 * n_lat, dev)
-        latent_bwd_ragged(lib, muls, eps, wsd[o:o + n_lat], tab, c, float(lambda_kl) / n_lat, d_muls)
+        latent_bwd_ragged(lib, muls, eps, wsd[o:o + n_lat], tab, c, float(lambda_kl) / n_kl, d_muls)
         pe.backward_content_params(flat, x, d_muls, grads, wse)
         ps.backward_params(flat, x, pd.d_emb(wsd), grads, wss)
         self._rag_last = ((pe, ps, pd), (wse, wss, wsd), tab)   # (the workspaces of the last step: saved rows, dec)
+        if packed and d is not None and (d.get_world_size() > 1 or self.config.get("allreduce_world1", False)):
+            self._allreduce_ragged(d, grads, losses)
         if not apply:
             if not sync:
                 return {"loss_rec": losses[0], "loss_kl": losses[1]}
@@ -385,6 +457,26 @@ class Solver(object):
             lambda_kl = self.kl_weight(iteration)
             data = next(self.train_iter)
             meta = self.ae_step(data, lambda_kl)
+            if iteration % self.args.summary_steps == 0:
+                self.logger.scalars_summary(f"{self.args.tag}/ae_train", meta, iteration)
+            print(f"AE:[{iteration + 1}/{n_iterations}], loss_rec={meta['loss_rec']:.2f}, "
+                  f"loss_kl={meta['loss_kl']:.2f}, lambda={lambda_kl:.1e}     ", end="\r")
+            if (iteration + 1) % self.args.save_steps == 0 or iteration + 1 == n_iterations:
+                self.save_model(iteration=iteration)
+                print()
+
+    def train_ragged(self, n_iterations):
+        """``train`` on whole utterances: batches from ``self.ragged_iter`` (a ``RaggedUtteranceFeed``; ``--ragged_feed``), steps by
+        ``ae_step_ragged``.  The feed repeats K tuples of lengths, and the step keeps three grad plans with their workspaces and one
+        table set per tuple: the model's ragged plan cache is raised to 3 K + 1 and this solver's table cache to K, so that after each
+        template's first visit nothing is created any more."""
+        feed = self.ragged_iter
+        K = int(feed.n_templates)
+        self.model.set_ragged_plan_cache(max(self.model._ragged_cap, 3 * K + 1))
+        self._rag_tables_cap = max(getattr(self, "_rag_tables_cap", 4), K)
+        for iteration in range(n_iterations):
+            lambda_kl = self.kl_weight(iteration)
+            meta = self.ae_step_ragged(next(feed), lambda_kl)
             if iteration % self.args.summary_steps == 0:
                 self.logger.scalars_summary(f"{self.args.tag}/ae_train", meta, iteration)
             print(f"AE:[{iteration + 1}/{n_iterations}], loss_rec={meta['loss_rec']:.2f}, "

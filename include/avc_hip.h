@@ -641,7 +641,9 @@ int avc_reparam_ragged(const float* muls, const float* eps, int S, const int* Tz
  * at row xoff[j] (xoff = prefix sums of T); dec / d_dec: block j is [M][out_len[j]] (frames contiguous) at float offset out_off[j] from the
  * pointer passed (avc_plan_ragged_out's offsets minus the first), out_len[j] >= T[j] >= 1: frames t < T[j] count, the crop tail
  * T[j] <= t < out_len[j] is ignored.  T_dev / xoff_dev / out_len_dev (int32) and out_off_dev (int64) are DEVICE tables of N entries;
- * T_max >= every out_len[j].  Latent block j (above; S = N) feeds the KL term.  n_rec = M sum(T), n_kl = c sum(Tz).
+ * T_max >= every out_len[j].  Latent block j (above; S = N) feeds the KL term.  n_rec = M sum(T), n_kl = c sum(Tz) -- or,
+ * on a data-parallel rank, those counts over ALL ranks' utterances: the rank then produces its share of the global means and of their
+ * gradient, and the shares add up (likewise lambda_kl_over_n of avc_latent_bwd_ragged).
  * OVERWRITES every element of every d_dec block exactly once: lambda_rec / n_rec (divided in double, rounded once) times sign(dec - x) for
  * t < T[j], 0 in the crop tail; losses[0] = mean |dec - x| over the n_rec kept elements, losses[1] = 0.5 mean(exp(ls) + mu^2 - 1 - ls)
  * over the n_kl latent elements; and the avc_loss_ragged_ws_floats(N, T_max) floats of ws (partial sums; -1 for a bad count). */
@@ -655,6 +657,19 @@ int avc_loss_ragged(const float* dec, const int* out_len_dev, const long* out_of
  * nothing else. */
 int avc_latent_bwd_ragged(const float* muls, const float* eps, const float* d_z, int S, const int* Tz_dev, const int* offz_dev, int Tz_max, int c,
                           float lambda_kl_over_n, float* d_muls, void* stream);
+
+/* ---- device-side feed of the ragged step (csrc/ragged_feed.hip): whole utterances, or crops of them, out of the HBM-resident corpus
+ * [n_rows][M] (fp32, mel bins contiguous: the corpus of avc_gather_segments) into the frame-major packed block the ragged grad plans and
+ * avc_loss_ragged read as x: out[(xoff[j] + t) M + m] = corpus[(starts[j] + t) M + m] for t < T[j].  T_dev / xoff_dev are the DEVICE int32
+ * tables of N entries avc_loss_ragged takes (xoff = prefix sums of T), starts_dev a DEVICE int64 table of N first rows; T_max >= every T[j]
+ * sizes the grid.  A segmented copy: 16 bytes per lane for an utterance whose run starts on a 16-byte boundary on both sides (starts[j] M
+ * and xoff[j] M multiples of 4, both pointers 16-byte aligned), 4 bytes per lane otherwise; the bits are the corpus's either way.
+ * READS rows starts[j] .. starts[j] + T[j] - 1 and nothing else, OVERWRITES the M sum(T) floats of out and nothing else; an utterance whose
+ * rows are not all inside [0, n_rows) is skipped as a whole (nothing read, its block left as it was): the caller validates its starts.
+ * ONLY ENQUEUES on `stream`: no allocation, no copy from the host, no synchronisation -- graph-capture safe.  0 on success, -1 for a null
+ * pointer or a bad count (N outside 1..65535; n_rows, M or T_max below 1). */
+int avc_gather_utterances(const float* corpus, long n_rows, int M, const long* starts_dev, const int* T_dev, const int* xoff_dev, int N, int T_max,
+                          float* out, void* stream);
 
 #ifdef __cplusplus
 }
