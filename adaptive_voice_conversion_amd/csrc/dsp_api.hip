@@ -162,6 +162,8 @@ int avc_dsp_deemphasis(const float* x, long L, float a, float* out, void* stream
 int avc_dsp_frame_power(const float* y, long L, int frame_length, int hop_length, float* out, void* stream) {
     if (!y || !out || frame_length < 2 || hop_length < 1) return -1;
     if (L <= frame_length / 2) return -6;
-    return avc_launch_dsp_frame_power(y, L, frame_length, hop_length, avc_dsp_num_frames(L, hop_length), out, (hipStream_t)stream);
+    // 1 + (L + 2 (frame_length / 2) - frame_length) / hop frames fit the padded signal: an ODD frame_length pads one sample less than it
+    // spans, and counting 1 + L / hop would cut a last frame that reaches one sample past the padding (index -1 at L = frame_length/2 + 1)
+    return avc_launch_dsp_frame_power(y, L, frame_length, hop_length, avc_dsp_num_frames(L - (frame_length & 1), hop_length), out, (hipStream_t)stream);
 }
 }

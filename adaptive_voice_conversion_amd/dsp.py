@@ -151,7 +151,7 @@ class MelDSP:
     def trim(self, y, top_db=60, frame_length=2048, hop_length=512):
         """librosa.effects.trim(y, top_db): the frame powers come from the device, the two indices are picked here."""
         y = self._wave(y)
-        nf = self.lib.avc_dsp_num_frames(y.numel(), hop_length)
+        nf = self.lib.avc_dsp_num_frames(y.numel() - (frame_length & 1), hop_length)   # (an odd frame pads one sample less than it spans)
         mse = torch.empty(nf, device=self.device)
         with self._dev():
             self._ok(self.lib.avc_dsp_frame_power(_P(y), y.numel(), frame_length, hop_length, _P(mse), self._stream()))

@@ -547,7 +547,7 @@ int avc_dsp_db_normalize(const float* in, int C, int T, float ref_db, float max_
 int avc_dsp_denormalize_amp(const float* in, int C, int T, float ref_db, float max_db, float* out, void* stream);
 int avc_dsp_preemphasis(const float* y, long L, float a, float* out, void* stream);        /* utils.py:60 (out != y) */
 int avc_dsp_deemphasis(const float* x, long L, float a, float* out, void* stream);         /* utils.py:104 lfilter([1], [1, -a]) */
-/* mean square of the frames of librosa.effects.trim (utils.py:57,107): out[1 + L/hop] */
+/* mean square of the frames of librosa.effects.trim (utils.py:57,107): out[1 + (L - frame_length % 2) / hop] */
 int avc_dsp_frame_power(const float* y, long L, int frame_length, int hop_length, float* out, void* stream);
 
 /* ---- op-level entry points (one per kernel family and direction) -------- */

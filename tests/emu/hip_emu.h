@@ -175,9 +175,23 @@ static inline f32x4_t mfma_16x16x4(float a, float b, f32x4_t c) {
 }  // namespace emu
 
 // device math that libm lacks (dsp.hip)
-static inline double cospi(double x) { return cos(M_PI * x); }
-static inline float cospif(float x) { return (float)cos(M_PI * (double)x); }
-static inline void sincospi(double x, double* s, double* c) { *s = sin(M_PI * x); *c = cos(M_PI * x); }
+// Like the device's, they reduce the argument BEFORE the multiplication by pi: exact 0 / +-1 at the multiples of 1/2 (cos(M_PI * 0.5) is
+// 6e-17, which a basis element that is exactly 0 on the GPU would inherit).
+static inline void sincospi(double x, double* s, double* c) {
+    double r = fmod(x, 2.0);                     // exact
+    if (r < 0) r += 2.0;
+    const int n = (int)floor(2.0 * r + 0.5);     // nearest multiple of 1/2: 0 .. 4
+    const double t = r - 0.5 * n;                // exact, |t| <= 1/4
+    const double s0 = sin(M_PI * t), c0 = cos(M_PI * t);
+    switch (n & 3) {
+        case 0: *s = s0; *c = c0; break;
+        case 1: *s = c0; *c = -s0; break;
+        case 2: *s = -s0; *c = -c0; break;
+        default: *s = -c0; *c = s0; break;
+    }
+}
+static inline double cospi(double x) { double s, c; sincospi(x, &s, &c); return c; }
+static inline float cospif(float x) { return (float)cospi((double)x); }
 
 #define __syncthreads() emu::block_barrier()
 #define __builtin_amdgcn_s_barrier() emu::block_barrier()
