@@ -220,6 +220,11 @@ def declare(lib):
     lib.avc_dsp_preemphasis.argtypes = [c_void_p, c_long, c_float, c_void_p, c_void_p]
     lib.avc_dsp_deemphasis.argtypes = [c_void_p, c_long, c_float, c_void_p, c_void_p]
     lib.avc_dsp_frame_power.argtypes = [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]
+    if hasattr(lib, "avc_dsp_frame_power_ragged"):   # (absent from older builds loaded through AVC_HIP_LIB for same-box A/B runs)
+        lib.avc_dsp_frame_power_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+        lib.avc_dsp_frames_ragged_preemph.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                                      c_void_p, c_void_p]
+        lib.avc_dsp_deemphasis_ragged.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]
     lib.avc_prof_end.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.avc_prof_class_name.argtypes = [c_int]
     lib.avc_prof_class_name.restype = ctypes.c_char_p

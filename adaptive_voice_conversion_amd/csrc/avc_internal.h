@@ -46,6 +46,12 @@ int avc_launch_dsp_denorm_amp(const float* in, int C, int T, float ref_db, float
 int avc_launch_dsp_preemph(const float* y, long L, float a, float* out, hipStream_t s);
 int avc_launch_dsp_deemph(const float* x, long L, float a, float* out, hipStream_t s);
 int avc_launch_dsp_frame_power(const float* y, long L, int frame_length, int hop, int n_frames, float* out, hipStream_t s);
+// packed utterances of different lengths at the two audio edges (dsp_ragged.hip)
+int avc_launch_dsp_frame_power_ragged(const float* y, const long* woff, const int* poff, int B, int n_frames, int frame_length, int hop, float* out,
+                                      hipStream_t s);
+int avc_launch_dsp_frames_ragged_preemph(const float* y, const long* woff, const int* toff, const long* bounds, int B, int Ttot, int hop, int n_fft,
+                                         int win, float a, float* frames, hipStream_t s);
+int avc_launch_dsp_deemph_ragged(const float* x, const long* woff, int B, float a, float* out, hipStream_t s);
 #define AVC_PACK_BATCH 16
 int avc_launch_pack_batch(const PackArgs* ps, int n, hipStream_t stream);
 #define AVC_PACK_PIECE 2048   // image elements per block of the one-launch pack (8 per thread): legacy pieces

@@ -19,18 +19,7 @@
 
 #include "avc_common.h"
 #include "avc_internal.h"
-
-static inline int dsp_blocks(long n) {
-    long b = (n + AVC_THREADS - 1) / AVC_THREADS;
-    return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
-// numpy.pad(mode='reflect') index for a pad shorter than the signal
-static __device__ __forceinline__ long dsp_reflect(long v, long L) {
-    if (v < 0) v = -v;
-    if (v >= L) v = 2 * (L - 1) - v;
-    return v;
-}
+#include "dsp_shared.h"   // dsp_blocks, dsp_reflect, dsp_find and the bodies shared with dsp_ragged.hip
 
 // which = 0: forward basis in state-dict layout [2F][win] (Cout = 2F, Cin = win);  which = 1: inverse basis [win][2F]
 __global__ void __launch_bounds__(AVC_THREADS) dsp_basis_kernel(int which, int n_fft, int win, float* W) {
@@ -92,15 +81,6 @@ __global__ void __launch_bounds__(AVC_THREADS) dsp_ola_kernel(const float* tf, i
 
 // ---- utterances of DIFFERENT lengths in one launch set: toff[b] = first frame (column) of utterance b, toff[B] = all frames;
 // utterance b has T_b = toff[b+1] - toff[b] frames and hop (T_b - 1) samples, stored back to back from sample hop (toff[b] - b)
-static __device__ __forceinline__ int dsp_find(const int* toff, int B, long key, int hop, bool samples) {
-    int lo = 0, hi = B - 1;   // largest b with start(b) <= key
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        const long start = samples ? (long)hop * (toff[mid] - mid) : (long)toff[mid];
-        if (start <= key) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 __global__ void __launch_bounds__(AVC_THREADS) dsp_frames_ragged_kernel(const float* y, const int* toff, int B, int hop, int n_fft, int win, float* frames) {
     const int n0 = (n_fft - win) / 2;
     const long TT = toff[B], total = (long)win * TT;
@@ -185,57 +165,18 @@ __global__ void __launch_bounds__(AVC_THREADS) dsp_denorm_amp_kernel(const float
 // utils.py:60: out[0] = y[0], out[i] = y[i] - a y[i-1]
 __global__ void __launch_bounds__(AVC_THREADS) dsp_preemph_kernel(const float* y, long L, float a, float* out) {
     for (long i = (long)blockIdx.x * AVC_THREADS + threadIdx.x; i < L; i += (long)gridDim.x * AVC_THREADS)
-        out[i] = i == 0 ? y[0] : y[i] - a * y[i - 1];
+        out[i] = dsp_preemph_at(y, i, a);
 }
 // utils.py:104: scipy.signal.lfilter([1], [1, -a], x): out[i] = x[i] + a out[i-1].  ONE workgroup of 1024 lanes, each a
 // contiguous run: local recurrence, then the carries in sequence (1024 steps), then out += a^(j+1) * carry_in.
 __global__ void __launch_bounds__(1024) dsp_deemph_kernel(const float* x, long L, float a, float* out) {
     __shared__ float last[1024], cin[1024], apow[1024];
-    const int tid = threadIdx.x;
-    const long run = (L + 1023) / 1024;
-    const long i0 = (long)tid * run, i1 = (i0 + run < L) ? i0 + run : L;
-    float v = 0.f, p = 1.f;
-    for (long i = i0; i < i1; ++i) {
-        v = x[i] + a * v;
-        out[i] = v;
-        p *= a;
-    }
-    last[tid] = v;
-    apow[tid] = p;
-    __syncthreads();
-    if (tid == 0) {
-        float c = 0.f;
-        for (int j = 0; j < 1024; ++j) {
-            cin[j] = c;
-            c = last[j] + apow[j] * c;
-        }
-    }
-    __syncthreads();
-    const float c = cin[tid];
-    if (c != 0.f) {
-        float q = a;
-        for (long i = i0; i < i1; ++i) {
-            out[i] += q * c;
-            q *= a;
-        }
-    }
+    dsp_deemph_body(x, L, a, out, last, cin, apow);
 }
 // mean square of the frames librosa.feature.rms(frame_length, hop_length, center=True) cuts (effects.trim, utils.py:57,107)
 __global__ void __launch_bounds__(AVC_THREADS) dsp_frame_power_kernel(const float* y, long L, int frame_length, int hop, float* out) {
     __shared__ float red[AVC_THREADS];
-    const int fr = blockIdx.x;
-    float s = 0.f;
-    for (int k = threadIdx.x; k < frame_length; k += AVC_THREADS) {
-        const float v = y[dsp_reflect((long)fr * hop + k - frame_length / 2, L)];
-        s += v * v;
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = AVC_THREADS / 2; o >= 1; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[fr] = red[0] / (float)frame_length;
+    dsp_frame_power_body(y, L, frame_length, hop, (long)blockIdx.x, red, out + blockIdx.x);
 }
 
 // --------------------------------------------------------------------------

@@ -166,4 +166,57 @@ int avc_dsp_frame_power(const float* y, long L, int frame_length, int hop_length
     // spans, and counting 1 + L / hop would cut a last frame that reaches one sample past the padding (index -1 at L = frame_length/2 + 1)
     return avc_launch_dsp_frame_power(y, L, frame_length, hop_length, avc_dsp_num_frames(L - (frame_length & 1), hop_length), out, (hipStream_t)stream);
 }
+
+// ---- B utterances of different lengths, packed back to back: utterance b is samples woff[b] .. woff[b+1] of one buffer (B + 1 int64,
+// woff[0] = 0, every utterance at least one sample).  Every table comes twice, as for avc_dsp_griffin_lim_ragged: the device copy the
+// kernels index through, and the HOST copy that is validated here -- a refused call launches nothing.
+static bool dsp_woff_ok(const long* woff_host, int B) {
+    if (woff_host[0] != 0) return false;
+    for (int b = 0; b < B; ++b)
+        if (woff_host[b + 1] <= woff_host[b]) return false;
+    return true;
+}
+
+// avc_dsp_frame_power of every utterance in ONE launch: the powers of utterance b go to out[poff[b] .. poff[b+1]), poff[b+1] - poff[b] =
+// 1 + (L_b - frame_length % 2) / hop, the count of the single entry point (poff: B + 1 int32 from 0)
+int avc_dsp_frame_power_ragged(const float* y, const long* woff, const long* woff_host, const int* poff, const int* poff_host, int B,
+                               int frame_length, int hop_length, float* out, void* stream) {
+    if (!y || !woff || !woff_host || !poff || !poff_host || !out || B < 1 || frame_length < 2 || hop_length < 1) return -1;
+    if (!dsp_woff_ok(woff_host, B) || poff_host[0] != 0) return -1;
+    for (int b = 0; b < B; ++b)
+        if (woff_host[b + 1] - woff_host[b] <= frame_length / 2) return -6;
+    for (int b = 0; b < B; ++b) {
+        const long nf = 1 + (woff_host[b + 1] - woff_host[b] - (frame_length & 1)) / hop_length;
+        if (nf > 0x7fffffffL - poff_host[b] || poff_host[b + 1] != poff_host[b] + (int)nf) return -1;
+    }
+    return avc_launch_dsp_frame_power_ragged(y, woff, poff, B, poff_host[B], frame_length, hop_length, out, (hipStream_t)stream);
+}
+
+// Pre-emphasis (utils.py:60) fused into the framing of librosa.stft (utils.py:63-66) for B utterances: utterance b is the sub-run
+// [woff[b] + s_b, woff[b] + e_b) of the packed buffer, (s_b, e_b) = bounds[2b], bounds[2b+1] (2B int64: what trim chose, or 0 and L_b); its
+// T_b = 1 + (e_b - s_b) / hop frames are columns toff[b] .. toff[b+1] - 1 of frames [win_length][Ttot], reflect-padded at the TRIMMED length.
+// -6 when an utterance has e_b - s_b <= n_fft / 2, -1 when toff disagrees with the bounds.  The STFT is avc_conv1d_fwd on frames.
+int avc_dsp_frames_ragged_preemph(const float* y, const long* woff, const long* woff_host, const int* toff, const int* toff_host, const long* bounds,
+                                  const long* bounds_host, int B, int n_fft, int hop_length, int win_length, float a, float* frames, void* stream) {
+    if (!dsp_geom_ok(n_fft, hop_length, win_length) || !y || !woff || !woff_host || !toff || !toff_host || !bounds || !bounds_host || !frames || B < 1)
+        return -1;
+    if (!dsp_woff_ok(woff_host, B) || toff_host[0] != 0) return -1;
+    for (int b = 0; b < B; ++b) {
+        const long s = bounds_host[2 * b], e = bounds_host[2 * b + 1];
+        if (s < 0 || e < s || e > woff_host[b + 1] - woff_host[b]) return -1;
+    }
+    for (int b = 0; b < B; ++b)
+        if (bounds_host[2 * b + 1] - bounds_host[2 * b] <= n_fft / 2) return -6;
+    for (int b = 0; b < B; ++b) {
+        const long Tb = 1 + (bounds_host[2 * b + 1] - bounds_host[2 * b]) / hop_length;
+        if (Tb > 0x7fffffffL - toff_host[b] || toff_host[b + 1] != toff_host[b] + (int)Tb) return -1;
+    }
+    return avc_launch_dsp_frames_ragged_preemph(y, woff, toff, bounds, B, toff_host[B], hop_length, n_fft, win_length, a, frames, (hipStream_t)stream);
+}
+
+// avc_dsp_deemphasis of every utterance in ONE launch, one workgroup each (x == out is allowed, as there)
+int avc_dsp_deemphasis_ragged(const float* x, const long* woff, const long* woff_host, int B, float a, float* out, void* stream) {
+    if (!x || !woff || !woff_host || !out || B < 1 || !dsp_woff_ok(woff_host, B)) return -1;
+    return avc_launch_dsp_deemph_ragged(x, woff, B, a, out, (hipStream_t)stream);
+}
 }

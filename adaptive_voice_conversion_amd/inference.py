@@ -100,10 +100,52 @@ class Inferencer(object):
         mel, _ = self.dsp().get_spectrograms(path)
         return torch.from_numpy(self.normalize(mel)).float()
 
+    def mels_from_wavs(self, wavs):
+        """``_mel_from_path`` for a LIST of wav paths / decoded waveforms in ONE front-end launch set (``MelDSP.get_spectrograms_batch``:
+        one upload, one read-back for all the trims) and ``normalize`` on the device.  Returns the list of normalised [T_b, n_mels] float32
+        DEVICE tensors, bit-equal to ``_mel_from_path`` per file: the arithmetic runs in the dtype of the attr arrays, as numpy's does."""
+        packed, _, toff = self.dsp()._spectrograms_packed(list(wavs))
+        if self.attr is not None:
+            mean, std = (torch.as_tensor(self.attr[k]).to(packed.device) for k in ("mean", "std"))
+            packed = ((packed.to(torch.promote_types(packed.dtype, mean.dtype)) - mean) / std).float()
+        return [packed[toff[b]:toff[b + 1]] for b in range(len(toff) - 1)]
+
+    def convert_wavs(self, sources, targets=None, emb=None, src_of=None, do_trim=True, n_iter=None, ragged=False):
+        """Wav to wav for many utterances: ``sources`` (and ``targets``, one per source: the voice of pair i) are wav paths or decoded
+        waveforms of any lengths.  ONE front-end launch set for all sources and targets (``mels_from_wavs``), the conversion on mels
+        that never leave the device in between, and ONE batched back end (``melspectrogram2wav_batch``).
+        The conversion of (source, target) pairs: by default every pair goes through the plan ``inference_one_utterance`` runs (the
+        uniform plan at batch 1), so the result is what the per-file path gives, to the bit; ``ragged=True`` converts all pairs in ONE
+        ragged launch set (``convert_batch``), whose InstanceNorm rows reduce in another order: the mels then agree with the per-file
+        path to about 1e-6, not to the bit.  With ``emb`` / ``src_of`` (an enrolled voice, a fan-out) the conversion is the ragged one.
+        Returns (list of float32 waveforms, list of converted denormalised mels)."""
+        sources = list(sources)
+        if (targets is None) == (emb is None):
+            raise ValueError("convert_wavs: pass exactly one of targets (one wav per source) and emb (speaker embeddings)")
+        if targets is not None:
+            targets = list(targets)
+            if len(targets) != len(sources):
+                raise ValueError(f"convert_wavs: {len(sources)} sources but {len(targets)} targets")
+            mels = self.mels_from_wavs(sources + targets)
+            pairs = list(zip(mels[:len(sources)], mels[len(sources):]))
+            if ragged:
+                converted = self.convert_batch(pairs)
+            else:
+                with torch.no_grad():
+                    converted = [self.model.inference(self.utt_make_frames(x), self.utt_make_frames(c)).transpose(1, 2).squeeze(0).cpu()
+                                 for x, c in pairs]
+        else:
+            converted = self.convert_batch(self.mels_from_wavs(sources), emb=emb, src_of=src_of)
+        out = [self.denormalize(m.numpy()) for m in converted]
+        return self.dsp().melspectrogram2wav_batch(out, do_trim=do_trim, n_iter=n_iter), out
+
     def inference_from_path(self):
         """The reference's command (one ``-source``, one ``-target``), and the enrolment workflow on top of it: several targets
         (``args.target`` a list: the voice is the mean embedding of the files), ``args.save_emb`` (write the enrolled embedding with
-        ``torch.save``; without ``args.source`` nothing is converted), ``args.emb`` (convert with a saved embedding instead of a target)."""
+        ``torch.save``; without ``args.source`` nothing is converted), ``args.emb`` (convert with a saved embedding instead of a target).
+        Several sources (``args.source`` a list): ``args.output`` is a directory, source ``name.wav`` is written to ``output/name.wav``
+        (a repeated name gets its position in front).  Whenever more than one file is read, all of them go through the front end in
+        one launch set (``mels_from_wavs``)."""
         dsp = self.dsp()
         if self.model._n_mels != dsp.hp.n_mels:
             raise ValueError(f"the model works on {self.model._n_mels}-mel features, get_spectrograms produces {dsp.hp.n_mels} "
@@ -115,22 +157,44 @@ class Inferencer(object):
             raise ValueError("give either -target (one or several wav files to enrol from) or -emb (a saved embedding), not both")
         if emb_path is None and not targets:
             raise ValueError("a target voice is needed: -target (one or several wav files) or -emb (a saved embedding)")
-        if len(targets) == 1 and emb_path is None and save_emb is None:   # the reference's path (inference.py:86-93)
-            conv_wav, conv_mel = self.inference_one_utterance(self._mel_from_path(self.args.source), self._mel_from_path(targets[0]))
+        source = getattr(self.args, "source", None)
+        many = isinstance(source, (list, tuple))
+        sources = list(source) if many else ([source] if source is not None else [])
+        files = sources + targets
+        mels = self.mels_from_wavs(files) if len(files) > 1 else [self._mel_from_path(f) for f in files]   # ONE front-end launch set
+        src_mels, tgt_mels = mels[:len(sources)], mels[len(sources):]
+        if len(targets) == 1 and emb_path is None and save_emb is None and not many:   # the reference's path (inference.py:86-93)
+            conv_wav, conv_mel = self.inference_one_utterance(src_mels[0], tgt_mels[0])
             self.write_wav_to_file(conv_wav, self.args.output)
             return conv_wav, conv_mel
         if emb_path is not None:
             emb = torch.load(emb_path, map_location="cpu")
         else:
-            emb = self.enroll([self._mel_from_path(t) for t in targets])
+            emb = self.enroll(tgt_mels)
         if save_emb is not None:
             torch.save(emb.detach().cpu(), save_emb)
-        if getattr(self.args, "source", None) is None:
+        if not sources:
             return None, None   # enrolment only
-        conv_mel = self.denormalize(self.convert_batch([self._mel_from_path(self.args.source)], emb=emb)[0].numpy())
-        conv_wav = self.mel2wav(conv_mel) if self.mel2wav is not None else dsp.melspectrogram2wav(conv_mel)
-        self.write_wav_to_file(conv_wav, self.args.output)
-        return conv_wav, conv_mel
+        conv_mels = [self.denormalize(m.numpy()) for m in self.convert_batch(src_mels, emb=emb)]
+        if self.mel2wav is not None:
+            conv_wavs = [self.mel2wav(m) for m in conv_mels]
+        else:
+            conv_wavs = dsp.melspectrogram2wav_batch(conv_mels) if many else [dsp.melspectrogram2wav(conv_mels[0])]
+        if not many:
+            self.write_wav_to_file(conv_wavs[0], self.args.output)
+            return conv_wavs[0], conv_mels[0]
+        for path, wav in zip(self.output_paths(sources, self.args.output), conv_wavs):
+            self.write_wav_to_file(wav, path)
+        return conv_wavs, conv_mels
+
+    @staticmethod
+    def output_paths(sources, out_dir):
+        """Where the conversions of several sources go: ``out_dir/<file name of the source>``; a name that occurs twice gets the
+        source's position in front (``1_name.wav``).  The directory is created."""
+        import os
+        os.makedirs(out_dir, exist_ok=True)
+        names = [os.path.basename(str(s)) for s in sources]
+        return [os.path.join(out_dir, n if names.count(n) == 1 else f"{i}_{n}") for i, n in enumerate(names)]
 
     def enroll(self, utterances):
         """Enrol a target voice: ``utterances`` are normalised [T, M] mels of ONE speaker, of any (unequal) lengths.  All of them go
@@ -236,10 +300,11 @@ def make_parser():
     parser.add_argument('-attr', '-a', help='attr file path')
     parser.add_argument('-config', '-c', help='config file path')
     parser.add_argument('-model', '-m', help='model path')
-    parser.add_argument('-source', '-s', help='source wav path')
+    parser.add_argument('-source', '-s', action='append',
+                        help='source wav path; may be given several times: -output is then a directory that receives one wav per source')
     parser.add_argument('-target', '-t', action='append',
                         help='target wav path; may be given several times: the voice is then enrolled from all of them (mean embedding)')
-    parser.add_argument('-output', '-o', help='output wav path')
+    parser.add_argument('-output', '-o', help='output wav path (with several -source: output directory)')
     parser.add_argument('-sample_rate', '-sr', help='sample rate', default=24000, type=int)
     parser.add_argument('-save_emb', help='write the enrolled speaker embedding here (torch.save); without -source nothing is converted')
     parser.add_argument('-emb', help='convert with a speaker embedding saved by -save_emb instead of -target')
@@ -247,8 +312,10 @@ def make_parser():
 
 
 def parse_args(argv=None):
-    """A single -target stays the string it has always been; several become a list."""
+    """A single -target / -source stays the string it has always been; several become a list."""
     args = make_parser().parse_args(argv)
+    if args.source is not None and len(args.source) == 1:
+        args.source = args.source[0]
     if args.target is not None and len(args.target) == 1:
         args.target = args.target[0]
     return args

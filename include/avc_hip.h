@@ -549,6 +549,22 @@ int avc_dsp_preemphasis(const float* y, long L, float a, float* out, void* strea
 int avc_dsp_deemphasis(const float* x, long L, float a, float* out, void* stream);         /* utils.py:104 lfilter([1], [1, -a]) */
 /* mean square of the frames of librosa.effects.trim (utils.py:57,107): out[1 + (L - frame_length % 2) / hop] */
 int avc_dsp_frame_power(const float* y, long L, int frame_length, int hop_length, float* out, void* stream);
+/* The two audio edges for B utterances of DIFFERENT lengths in one launch each.  The waveforms lie back to back in one buffer:
+ * utterance b is samples woff[b] .. woff[b+1] (woff: B + 1 device int64 from 0, every utterance at least one sample).  Every table
+ * comes twice, as for avc_dsp_griffin_lim_ragged: the device copy the kernels index through unchecked and the HOST copy validated here;
+ * a refused call launches nothing.  Each result is bit-equal to the single-utterance entry point called per utterance.
+ * frame_power_ragged: utterance b's powers at out[poff[b] .. poff[b+1]) (poff: B + 1 int32 from 0, poff[b+1] - poff[b] = the frame count of
+ *   avc_dsp_frame_power; -1 otherwise); -6 when an utterance has L_b <= frame_length / 2.
+ * frames_ragged_preemph: avc_dsp_preemphasis fused into the framing of avc_dsp_stft.  Utterance b is the sub-run [s_b, e_b) of its
+ *   samples, (s_b, e_b) = bounds[2b], bounds[2b+1] (2B int64: the trim indices, or 0 and L_b); frames is [win_length][Ttot] with its
+ *   T_b = 1 + (e_b - s_b) / hop frames in columns toff[b] .. toff[b+1] - 1 (toff: B + 1 int32 from 0; -1 when it disagrees with the bounds);
+ *   -6 when an utterance has e_b - s_b <= n_fft / 2.  spec = avc_conv1d_fwd(basis_fwd, frames) as inside avc_dsp_stft.
+ * deemphasis_ragged: avc_dsp_deemphasis on every utterance, one workgroup each (x == out allowed). */
+int avc_dsp_frame_power_ragged(const float* y, const long* woff, const long* woff_host, const int* poff, const int* poff_host, int B,
+                               int frame_length, int hop_length, float* out, void* stream);
+int avc_dsp_frames_ragged_preemph(const float* y, const long* woff, const long* woff_host, const int* toff, const int* toff_host, const long* bounds,
+                                  const long* bounds_host, int B, int n_fft, int hop_length, int win_length, float a, float* frames, void* stream);
+int avc_dsp_deemphasis_ragged(const float* x, const long* woff, const long* woff_host, int B, float a, float* out, void* stream);
 
 /* ---- op-level entry points (one per kernel family and direction) -------- */
 long avc_packed_weight_floats(int Cout, int Cin, int KS, int dgrad);
